@@ -4,6 +4,15 @@
 Contract: `python bench.py --gpus N --steps K --warmup W` (N>1: launched by
 torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: it sets up, warms up (a short time-based pre-roll, then W steps), times the K
+steps, writes its outputs if `--dump-outputs DIR` is given, and prints the line (`value`, `ms_per_step` = wall time of one
+timed step, and the roofline of the timed launches).  Everything else -- the overlap region, the copy ceilings, the parity
+launch, the `configs` leg and the CPU baseline -- runs only with `--full` (each can still be left out there by its `--no-*`).
+
+`--dump-outputs DIR` = after the timed steps, a fixed sample (positions drawn by a seeded generator) of the frames the last
+            timed step produced, as float32 DIR/Y.npy, U.npy, V.npy (at N>1: rankR_Y.npy ... per rank), 48 MiB in all.  The
+            frames and the seed state are set afresh after the pre-roll, so the same arguments give the same files every run.
+
 Workload (BASELINE.json `metric` / configs[4]): 7680x4320 10-bit 4:2:0, cfg fgs_sei
 (8 luma patterns, per-sample pattern selection), seed 12345, synthetic frames of uniformly
 random 10-bit samples generated on the GPU and resident in HBM before the timed region.
@@ -17,14 +26,14 @@ frames' worth at every N ("weak").  At N=1 a step is `batch` whole frames in one
 `value`   = luma pixels of all frames of all ranks / wall time          [Mpixels/s]
 `roofline`= algorithmic bytes per launch (4 B per Y/Cb/Cr sample: one read + one write of
             2 bytes) / mean launch duration from HIP events on the launching stream.
-`cpu_baseline` = the REAL reference hardware layer (oracle/_ref/libvfgs_ref.so, kind
+`cpu_baseline` = (`--full`) the REAL reference hardware layer (oracle/_ref/libvfgs_ref.so, kind
             "reference") if that prebuilt file travelled to this box, else this repo's oracle
             ("port"), one host core, on a bounded number of frames of the same workload.
-`parity_checked` = after the timed region one more launch of exactly the timed shape (same entry point, same frames per
+`parity_checked` = (`--full`; null otherwise) after the timed region one more launch of exactly the timed shape (same entry point, same frames per
             launch, in place) runs on freshly generated frames from a reset seed state, and every frame of it is compared
             with the oracle on the host (each rank its own stripes); true only if every byte and the seed registers agree.
 
-`configs` (N=1 only) = BASELINE.json configs[0..3] -- 1080p fgs_sei / ff_test1, 2160p ar_test1, 2160p 8-bit 4:4:4 AFGS1 -- each at the
+`configs` (`--full`, N=1 only) = BASELINE.json configs[0..3] -- 1080p fgs_sei / ff_test1, 2160p ar_test1, 2160p 8-bit 4:4:4 AFGS1 -- each at the
             stated frames per launch: launch duration (HIP events, plain stream), fraction of the 8 TB/s peak, the kernel the
             library reports having dispatched (vfgs_hip_last_launch_info), and a parity check of that shape against the oracle.
 A parity failure anywhere withholds the numbers: the line then carries `error` instead of `value`, and the exit code is 1.
@@ -266,6 +275,24 @@ def bench_configs(h, stream, steps_ms=60.0, cpu_seconds=2.5, out=None):
     return out
 
 
+DUMP_SAMPLES = {"Y": 8 << 20, "U": 2 << 20, "V": 2 << 20}     # float32: 48 MiB in all, split over the ranks
+
+
+def dump_outputs(dirname, buf, ny, nc, world, rank):
+    """--dump-outputs: a fixed sample of the frames in `buf` (one buffer set, [Y of every frame | U | V]) as float32 .npy files.
+    The positions come from a seeded generator and are sorted, so two runs (or two builds) write sample for sample the same places."""
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(20261016 + rank)
+    for name, off, n in (("Y", 0, ny), ("U", ny, nc), ("V", ny + nc, nc)):
+        k = DUMP_SAMPLES[name] // world
+        idx = np.arange(n) if n <= k else np.sort(rng.integers(0, n, k))
+        got = buf[torch.from_numpy(idx + off).to(buf.device)].cpu().numpy().view(np.uint16)
+        np.save(d / f"{'' if world == 1 else f'rank{rank}_'}{name}.npy", got.astype(np.float32))
+
+
 def gpu_numa_cpus(index, sysfs="/sys"):
     """CPUs of the NUMA node GPU `index` (HIP order) hangs off, from sysfs -- nothing here touches the GPU.  None if it cannot be told."""
     try:
@@ -319,6 +346,10 @@ def main():
     # the first ~10 ms of launches of a process run 4-8 % slower (clocks / TLBs settling); an untimed, time-based
     # pre-roll in front of --warmup makes the line independent of how few --steps/--warmup the caller asks for
     ap.add_argument("--preroll-ms", type=float, default=150.0, help="untimed launches for at least this long before --warmup")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: overlap region, copy ceilings, parity launch, configs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a fixed sample of the frames the last timed step produced to DIR/<plane>.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-ceiling", action="store_true", help="skip the same-process copy ceiling")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
@@ -329,6 +360,11 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the post-timing parity launch")
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE.json configs[0..3] leg (N=1 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # (the legs beside the headline run only with --full; their --no-* options leave one of them out there)
+    if not args.full:
+        args.no_cpu = args.no_ceiling = args.no_region = args.no_parity = args.no_configs = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one.  A child process (never exec: this box forbids replacing a process image once
@@ -419,6 +455,12 @@ def main():
             n_pre += 1
         torch.cuda.synchronize()
     preroll_ms = (time.perf_counter() - t0) * 1e3
+    # the pre-roll ran a time-dependent number of launches on these frames: the warmup starts again from the frames and the seed
+    # the allocation made, so that what the last timed step computes (--dump-outputs) depends on the arguments alone
+    g.manual_seed(1 + rank)
+    for b in sets:
+        b.random_(0, 1024, generator=g)
+    h.set_seed(next(a for op, a, _, _ in T.load_trace(TRACE) if op == T.OP_SEED))
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
@@ -435,6 +477,8 @@ def main():
     barrier()
     launch_ms = ev0.elapsed_time(ev1) / args.steps     # same stream as the kernels (torch's current stream)
     launch_info = h.last_launch_info()                 # what the timed launches dispatched (the library's own record)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sets[(args.warmup + args.steps - 1) % pool], ny, nc, world, rank)
 
     # ---- second leg (reported beside the contract's numbers, never as them): the same K launches inside an overlap region
     # (include/vfgs_hip.h: independent frames, the library alternates two internal streams, so one launch's tail overlaps the

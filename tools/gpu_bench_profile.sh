@@ -43,6 +43,7 @@ if 'hbm_traffic' in out:
 print(json.dumps(out, indent=1))
 PY
 # the bench lines last: they read profiles/hbm_traffic.json written above (same kernel source, same box)
-python bench.py --steps 20 --warmup 5 > gpurun_out/bench_driver_args.json 2> gpurun_out/bench_default.err; cat gpurun_out/bench_driver_args.json
-python bench.py > gpurun_out/bench_default.json 2>> gpurun_out/bench_default.err; cat gpurun_out/bench_default.json
-python bench.py --batch 1 --steps 1000 --warmup 300 --pool 24 --no-cpu --no-configs > gpurun_out/bench_b1.json 2>> gpurun_out/bench_default.err; cat gpurun_out/bench_b1.json
+R=${OUT_DIR:-bench_outputs}; mkdir -p "$R"     # where the bench lines go
+python bench.py --full --steps 20 --warmup 5 > $R/bench_driver_args.json 2> $R/bench_default.err; cat $R/bench_driver_args.json
+python bench.py --full > $R/bench_default.json 2>> $R/bench_default.err; cat $R/bench_default.json
+python bench.py --full --batch 1 --steps 1000 --warmup 300 --pool 24 --no-cpu --no-configs > $R/bench_b1.json 2>> $R/bench_default.err; cat $R/bench_b1.json

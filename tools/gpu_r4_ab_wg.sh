@@ -12,4 +12,5 @@ for l in sys.stdin:
     d = json.loads(l); print('%-50s x%d %8.3f us/launch' % (d['workload'], d['frames_per_launch'], d['launch_us']))"; done
 } > gpurun_out/r04_ab1_wg_bytes_vs_batch.log 2>&1
 cat gpurun_out/r04_ab1_wg_bytes_vs_batch.log
-python bench.py --steps 20 --warmup 5 > gpurun_out/r04_bench_a.json 2> gpurun_out/r04_bench_a.err; echo "bench rc $?"; cat gpurun_out/r04_bench_a.json; tail -5 gpurun_out/r04_bench_a.err
+R=${OUT_DIR:-bench_outputs}; mkdir -p "$R"     # where the bench line goes
+python bench.py --full --steps 20 --warmup 5 > $R/r04_bench_a.json 2> $R/r04_bench_a.err; echo "bench rc $?"; cat $R/r04_bench_a.json; tail -5 $R/r04_bench_a.err

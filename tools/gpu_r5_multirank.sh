@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out/r05_multirank_full_rehearsal.jsonl
 : > $OUT
 for n in ${RANKS:-2 4 5}; do for sc in weak strong; do
-  timeout -k 10 240 python bench.py --gpus $n --rehearse-on-one-gpu --scaling $sc --steps 20 --warmup 5 --no-ceiling --no-region 2>> gpurun_out/r05_multirank_full.err >> $OUT || echo "{\"error\": \"gpus $n $sc rc $?\"}" >> $OUT
+  timeout -k 10 240 python bench.py --full --gpus $n --rehearse-on-one-gpu --scaling $sc --steps 20 --warmup 5 --no-ceiling --no-region 2>> "${OUT%/*}/r05_multirank_full.err" >> $OUT || echo "{\"error\": \"gpus $n $sc rc $?\"}" >> $OUT
 done; done
 python3 - <<'PY'
 import json
