@@ -98,6 +98,26 @@ void vfgs_hip_shutdown(void);
  * only ever lives for one process; a long-lived library needs one. */
 void vfgs_hip_reset_state(void);
 
+/* Luma / chroma mix of the chroma look-up index (AFGS1: cb_mult, cb_luma_mult, cb_offset; off at power-on and after
+ * vfgs_hip_reset_state, and then every result is the reference's).  For component c (1 = Cb, 2 = Cr) with a mix, the
+ * index of BOTH look-ups (pattern LUT, scale LUT) of the chroma sample C at column cx of row cy is not C >> (depth - 8)
+ * (vfgs_hw.c:211) but m >> (depth - 8), where, with L the luma plane and C the chroma plane as they are BEFORE the call
+ * adds any grain, W the luma width of the call, 32-bit arithmetic and arithmetic shifts:
+ *   avgL = csubx == 2 ? (L[cy * csuby][2 cx] + L[cy * csuby][min(2 cx + 1, W - 1)] + 1) >> 1 : L[cy * csuby][cx]
+ *   m    = clip(((avgL * luma_mult + C * chroma_mult) >> 6) + offset * (1 << (depth - 8)), 0, (1 << depth) - 1)
+ * luma_mult, chroma_mult: units of 1/64, -128..127; offset: 8-bit code values, -256..255.  (0, 64, 0) is neutral.
+ * Nothing else changes: the grain added to luma, the seed registers, clipping.  Every processing entry point of this
+ * header honours an active mix, in place (the chroma planes are then computed in a launch of their own in front of luma's)
+ * and out of place, with three exceptions that REFUSE with error 38 and change nothing: a programmed model that needs a
+ * general-form pattern bank (a pattern LUT that selects more than one pattern; a one-pattern model wider than 8192 samples
+ * at 4:2:2 or 4:4:0) -- the kernels of the mix exist for the one-pattern banks of the AFGS1 models --, and
+ * vfgs_add_grain_stripe / vfgs_hip_add_grain_frames_host while several devices are set (vfgs_hip_init_devices).  While a
+ * mix is active vfgs_add_grain_line computes line by line (no look-ahead).
+ * set: 0, or error 37 (component or range) with nothing changed.  get: out[4] = { luma_mult, chroma_mult, offset, active }. */
+int vfgs_hip_set_chroma_mix(int c, int luma_mult, int chroma_mult, int offset);
+void vfgs_hip_clear_chroma_mix(void);
+int vfgs_hip_get_chroma_mix(int c, int out[4]);
+
 /* Device-resident stripe / frame: dY/dU/dV are DEVICE pointers to the first line of the
  * stripe (dU/dV: chroma row y/csuby); 16-byte aligned, pitch*bytes_per_sample % 16 == 0,
  * stride >= 16*ceil(width/16) (the reference writes whole 16-sample blocks, SURVEY 8a
@@ -264,7 +284,8 @@ int vfgs_hip_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, c
  * vfgs_hip_add_grain_frames_host): after a walk through the line call the record describes such a stripe launch.  `kernel` is the instantiation's name as the
  * profiler prints it (e.g. "grain_rw_kernel<10,2,2,false,false,true,false,false>": depth, chroma subsampling
  * x / y, 8-bit destination of a 10-bit path, luma one-pattern form, chroma one-pattern form, rows walked in parts,
- * persistent luma workgroups).  Returns 0, or -1 when nothing has been launched yet. */
+ * persistent luma workgroups; with a chroma mix active "grain_mix_kernel<10,2,2,false,false>": depth, chroma subsampling x / y,
+ * 8-bit destination, rows walked in parts -- an in-place call is two launches of it).  Returns 0, or -1 when nothing has been launched yet. */
 typedef struct vfgs_hip_launch_info {
 	int depth, csubx, csuby;          /* sample depth and chroma format the launch was compiled for */
 	int out8;                         /* 1: 10-bit source narrowed to 8 bit in the store */

@@ -83,6 +83,16 @@ void vfgs_init_afgs1(fgs_afgs1* cfg);
 
 /* ---- extensions ---------------------------------------------------------------------- */
 
+/* AFGS1 says how strong the chroma grain is at a sample by a mix of the co-located luma and the chroma sample (cb_mult,
+ * cb_luma_mult, cb_offset; the same for Cr; the luma alone with chroma_scaling_from_luma).  The reference reads the fields
+ * and drops them (vfgs_fw.c:706), and so does vfgs_init_afgs1 by default.  With this switch on (process-wide; a process
+ * that never calls it takes the environment variable VFGS_HIP_AFGS1_CHROMA_MIX=1 as `enable`, which is how the unchanged
+ * reference CLI linked against this library gets it) vfgs_init_afgs1 additionally programs the hardware layer's mix
+ * (vfgs_hip_set_chroma_mix, vfgs_hip.h) for Cb and Cr:
+ *   chroma_scaling_from_luma ? (64, 0, 0) : (cb_luma_mult - 128, cb_mult - 128, cb_offset - 256).
+ * With the switch off vfgs_init_afgs1 clears the mix; vfgs_init_sei always clears it. */
+void vfgs_hip_afgs1_chroma_mix(int enable);
+
 /* One grain pattern to be generated on the device into pattern slot `index`. */
 typedef struct vfgs_hip_pattern_job {
 	int32_t kind;       /* 0: frequency filtered (vfgs_fw.c:362-408), 1: auto-regressive (vfgs_fw.c:410-502) */

@@ -63,6 +63,8 @@ def main():
                                                         "as a list of plane pointers: vfgs_hip_add_grain_frame_list_dev (inplace mode)")
     ap.add_argument("--width", type=int, default=0, help="override the picture width (experiments)")
     ap.add_argument("--height", type=int, default=0, help="override the picture height (experiments)")
+    ap.add_argument("--mix", default="", help="luma_mult,chroma_mult,offset: the same luma / chroma mix of the look-up index for Cb and Cr "
+                                                "(vfgs_hip_set_chroma_mix; one-pattern models, e.g. configs 3, 5, 7, 9)")
     ap.add_argument("--stride", type=int, default=0, help="luma row pitch in samples (default: the width; chroma: stride / subx), inplace mode only (experiments)")
     args = ap.parse_args()
     name, w, hh, depth, (sx, sy), trace, kernel = CONFIGS[args.config]
@@ -76,6 +78,10 @@ def main():
         hw.load(os.environ["VFGS_LIB"])      # a variant build (tools/gpu_variants.sh)
     h = hw.VfgsHip(device=0)
     T.replay(h, T.load_trace(trace))
+    if args.mix:
+        for c in (1, 2):
+            h.set_chroma_mix(c, *map(int, args.mix.split(",")))
+        name += " [mix %s]" % args.mix
     dt = torch.int16 if depth > 8 else torch.uint8
     sz = 2 if depth > 8 else 1
     g = torch.Generator(device="cuda").manual_seed(3)
@@ -180,7 +186,7 @@ def main():
     nbytes = (sz + (1 if args.mode == "copy8" else sz)) * samples
     info = h.last_launch_info()
     kernel = info["kernel"] if info else kernel
-    print(json.dumps({"config": args.config, "workload": name, "content": args.content, "mode": args.mode, "frame_list": bool(args.list), "streams": args.streams, "overlap_region": bool(args.overlap), "kernel": kernel, "frames_per_launch": args.batch, "steps": args.steps,
+    print(json.dumps({"config": args.config, "workload": name, "mix": args.mix, "content": args.content, "mode": args.mode, "frame_list": bool(args.list), "streams": args.streams, "overlap_region": bool(args.overlap), "kernel": kernel, "frames_per_launch": args.batch, "steps": args.steps,
                       "launch_us": round(launch_us, 2), "host_us_per_call": round(host_us, 2), "us_per_frame": round(us, 3), "algorithmic_bytes_per_frame": int(nbytes),
                       "GBps": round(nbytes / us / 1e3, 1), "frac_of_8TBps": round(nbytes / us / 1e3 / 8000, 4),
                       "Mpixels_per_s": round(w * hh / us, 1), "Msamples_per_s": round(samples / us, 1)}), flush=True)

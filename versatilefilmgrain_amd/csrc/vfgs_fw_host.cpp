@@ -4,11 +4,12 @@
 // Only the small tables are computed here (scale / pattern LUTs, shifts, seed, the list of
 // distinct patterns); the patterns themselves are generated on the GPU by
 // vfgs_hip_generate_patterns (vfgs_fw_kernel.hip).  Like the reference's firmware this file is a
-// pure client of the hardware-layer interface; it keeps no state of its own.
+// pure client of the hardware-layer interface; the one thing it keeps is the switch of vfgs_hip_afgs1_chroma_mix.
 //
 // The derivations follow the reference line by line where the result depends on it, including
 // its oddities (each is marked QUIRK), because parity is judged on the bytes the hardware layer
 // ends up with (tests/golden/traces).
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +31,16 @@ constexpr int kMaxPatterns = 8;   // VFGS_MAX_PATTERNS, vfgs_hw.h:49
 	fprintf(stderr, "\n");
 	va_end(ap);
 	abort();   // the reference asserts (vfgs_fw.c:459, :656)
+}
+
+// vfgs_hip_afgs1_chroma_mix: -1 = never called, the environment decides
+std::atomic<int> g_afgs1_mix{-1};
+
+bool afgs1_mix_on()
+{
+	static const bool env_on = [] { const char* e = getenv("VFGS_HIP_AFGS1_CHROMA_MIX"); return e && e[0] == '1'; }();
+	const int v = g_afgs1_mix.load();
+	return v < 0 ? env_on : v != 0;
 }
 
 void generate(const vfgs_hip_pattern_job* jobs, int n)
@@ -222,6 +233,12 @@ void vfgs_init_sei(fgs_sei* cfg)
 	}
 	generate(jobs, njobs);
 	vfgs_set_scale_shift(cfg->log2_scale_factor - (cfg->model_id ? 1 : 0));   // vfgs_fw.c:644
+	vfgs_hip_clear_chroma_mix();      // an SEI model indexes chroma by the chroma sample
+}
+
+void vfgs_hip_afgs1_chroma_mix(int enable)
+{
+	g_afgs1_mix.store(enable != 0);
 }
 
 void vfgs_init_afgs1(fgs_afgs1* cfg)
@@ -270,6 +287,17 @@ void vfgs_init_afgs1(fgs_afgs1* cfg)
 
 	vfgs_set_scale_shift(cfg->grain_scaling - 6);
 	vfgs_set_legal_range(cfg->clip_to_restricted_range);
+
+	// cb_mult / cb_luma_mult / cb_offset (and Cr's): parsed and dropped by the reference (vfgs_fw.c:706); with the switch of
+	// vfgs_hip_afgs1_chroma_mix they become the hardware layer's luma / chroma mix, otherwise the index stays the chroma sample
+	vfgs_hip_clear_chroma_mix();
+	if (afgs1_mix_on())
+	{
+		const bool cfl = cfg->chroma_scaling_from_luma != 0;
+		if (vfgs_hip_set_chroma_mix(1, cfl ? 64 : cfg->cb_luma_mult - 128, cfl ? 0 : cfg->cb_mult - 128, cfl ? 0 : (int)cfg->cb_offset - 256) ||
+		    vfgs_hip_set_chroma_mix(2, cfl ? 64 : cfg->cr_luma_mult - 128, cfl ? 0 : cfg->cr_mult - 128, cfl ? 0 : (int)cfg->cr_offset - 256))
+			fw_die("AFGS1 chroma mix: %s", vfgs_hip_last_error_string());
+	}
 }
 
 }  // extern "C"

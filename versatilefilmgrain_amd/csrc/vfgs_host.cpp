@@ -923,6 +923,11 @@ State g_states[kMaxDevices];
 thread_local State* g_cur = nullptr;
 int g_ndev = 1;
 
+// Luma / chroma mix of the chroma look-up index (vfgs_hip_set_chroma_mix): Cb, Cr x { luma_mult, chroma_mult, offset, active }.
+// Process-wide like the rest of the programmed state; not replicated to the devices of vfgs_hip_init_devices (those calls refuse it).
+int g_mix[2][4] = {};
+bool mix_active() { return g_mix[0][3] || g_mix[1][3]; }
+
 State& S()
 {
 	return g_cur ? *g_cur : g_states[0];
@@ -1385,9 +1390,14 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	bool form_one_y = false, form_one_c = false;   // the form the table image will have (upload_tables below)
 	digest_pluts(s);
 	const bool wide = nparts > 1;           // rows walked in parts: not every form of the table image has such a kernel (image_form)
-	if (image_is_current(s, wide)) form_one_y = s.img_one_y;
+	if (image_is_current(s, wide)) { form_one_y = s.img_one_y; form_one_c = s.img_one_c; }
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
-	(void)form_one_c;
+	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
+	const bool mix = mix_active();
+	if (mix && !(form_one_y && form_one_c))
+		return fail(38, "a chroma mix is active and the programmed model needs a general-form pattern bank (%s rows): not supported", wide ? "wide" : "ordinary");
+	if (mix && &s != &g_states[0])
+		return fail(38, "a chroma mix is active: not supported on the devices of vfgs_hip_init_devices");
 	for (int pass = 0; pass < 3; pass++)
 	{
 		long waves = 0;
@@ -1517,6 +1527,36 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	const bool in_region = g_states[0].ov.active && (stream == g_states[0].ov.s[0] || stream == g_states[0].ov.s[1]);
 	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + 2 * cext) >= (64u << 20)) ? 1 : 0;
 #endif
+	if (mix)
+	{
+		if (!(s.img_one_y && s.img_one_c) || persist) return fail(19, "internal: the table image is not the form the chroma mix was admitted for");
+		a.mix_kernel = 1;
+		a.mix_lw = (int)width;
+		for (int c = 0; c < 2; c++)
+		{
+			a.mix[c][0] = g_mix[c][0]; a.mix[c][1] = g_mix[c][1];
+			a.mix[c][2] = g_mix[c][2] * (1 << s.bs);
+			a.mix[c][3] = g_mix[c][3];
+		}
+		// Chroma reads the luma of BEFORE this call.  Where a destination luma plane shares bytes with a source luma plane (in place) the
+		// luma workgroups must not run beside the chroma workgroups: two launches on the stream, chroma first.  Workgroup scheduling order
+		// is never relied on.
+		const uint64_t dext = dg.out8 ? (uint64_t)part_h * dg.stride : yext, dfp = dg.out8 ? dg.ypitch : ypitch;
+		auto meet = [](uintptr_t p, uint64_t pn, uintptr_t q, uint64_t qn) { return p < q + qn && q < p + pn; };
+		bool shared = false;
+		if (!list)     // (frames at a constant pitch: the extents of all frames together)
+			shared = meet((uintptr_t)sY, (uint64_t)(nframes - 1) * ypitch + yext, (uintptr_t)dY, (uint64_t)(nframes - 1) * dfp + dext);
+		else
+			for (unsigned i = 0; i < nframes && !shared; i++)
+				for (unsigned j = 0; j < nframes && !shared; j++)
+					shared = meet((uintptr_t)list->src[0][i], yext, (uintptr_t)list->dst[0][j], dext);
+		if (shared)
+		{
+			a.mix_planes = 1;      // chroma planes only
+			HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, true, true, wide, false, (int)grid, stream));
+			a.mix_planes = 2;      // luma only
+		}
+	}
 	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist, (int)grid, stream));
 	// the stream of the batches behind this one, while the GPU works on this one.  (Failing to work ahead is not a failure of THIS call, which is
 	// queued and whose registers have moved: the next call then builds its image in its own stream.)
@@ -1546,6 +1586,13 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		const vfgs::ImageLayout L = vfgs::layout_of(s.csubx, s.csuby, s.img_one_y, s.img_one_c, s.bs == 0);
 		li.lds_bytes_per_workgroup = vfgs::lds_allocation(s.bs != 0, s.img_one_y, s.img_one_c, wide, L.lds_bytes + vfgs::kParamBytes);     // (what the kernel allocates)
 		vfgs::describe_launch(li.kernel, sizeof li.kernel, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist);
+		if (mix)
+		{
+			// (the kernels of the mix: depth, chroma subsampling x / y, 8-bit destination, rows walked in parts; `launches` counts both launches of an in-place call)
+			li.lds_bytes_per_workgroup = vfgs::mix_lds_allocation(L.lds_bytes + vfgs::kParamBytes);
+			snprintf(li.kernel, sizeof li.kernel, "grain_mix_kernel<%d,%d,%d,%s,%s>", 8 + s.bs, s.csubx, s.csuby, dg.out8 ? "true" : "false", wide ? "true" : "false");
+			if (a.mix_planes) li.launches++;
+		}
 		g_last_launch_valid = true;
 	}
 	return 0;
@@ -2018,7 +2065,9 @@ int line_call(void* Y, void* U, void* V, unsigned y, unsigned width)
 	if (int e = ensure_init(-1)) return e;
 	State::LineAhead& la = s.la;
 	static const bool env_on = [] { const char* e = getenv("VFGS_HIP_LINE_LOOKAHEAD"); return !(e && e[0] == '0'); }();
-	if (!la.enabled || !env_on)
+	// (a mix makes a chroma line depend on the luma line above it as well: the look-ahead's "unchanged input bytes" test does not cover
+	// that, so the line call computes line by line while a mix is active)
+	if (!la.enabled || !env_on || mix_active())
 		return run_host(Y, U, V, y, width, 1, 0, 0);
 
 	const uint8_t *cY = (const uint8_t*)Y, *cU = (const uint8_t*)U, *cV = (const uint8_t*)V;
@@ -2246,6 +2295,7 @@ int on_all_devices(F&& fn)
 int run_host_multi(void* Y, void* U, void* V, unsigned y, unsigned width, unsigned height, unsigned stride, unsigned cstride)
 {
 	// a stripe of less than one block row per device is not worth the threads (and a 1-line call has no pitch to split by)
+	if (g_ndev > 1 && mix_active()) return fail(38, "a chroma mix is active: not supported with several devices (vfgs_hip_init_devices)");
 	if (g_ndev == 1 || height < 16u * g_ndev)
 		return run_host(Y, U, V, y, width, height, stride, cstride);
 	return on_all_devices([&](int d) {
@@ -2258,6 +2308,7 @@ int run_host_multi(void* Y, void* U, void* V, unsigned y, unsigned width, unsign
 int run_host_frames_multi(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width, unsigned height,
                           unsigned stride, unsigned cstride)
 {
+	if (g_ndev > 1 && mix_active()) return fail(38, "a chroma mix is active: not supported with several devices (vfgs_hip_init_devices)");
 	if (g_ndev == 1 || height < 16u * g_ndev)
 		return run_host_frames(Y, U, V, nframes, width, height, stride, cstride, 0, height);
 	return on_all_devices([&](int d) {
@@ -2464,6 +2515,32 @@ void vfgs_hip_line_lookahead(int enable)
 	S().la.valid = false;
 }
 
+int vfgs_hip_set_chroma_mix(int c, int luma_mult, int chroma_mult, int offset)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (c < 1 || c > 2) return fail(37, "vfgs_hip_set_chroma_mix: component %d (1 = Cb, 2 = Cr)", c);
+	if (luma_mult < -128 || luma_mult > 127 || chroma_mult < -128 || chroma_mult > 127 || offset < -256 || offset > 255)
+		return fail(37, "vfgs_hip_set_chroma_mix: %d, %d, %d outside -128..127, -128..127, -256..255", luma_mult, chroma_mult, offset);
+	S().gen++;
+	g_mix[c - 1][0] = luma_mult; g_mix[c - 1][1] = chroma_mult; g_mix[c - 1][2] = offset; g_mix[c - 1][3] = 1;
+	return 0;
+}
+
+void vfgs_hip_clear_chroma_mix(void)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	memset(g_mix, 0, sizeof g_mix);
+}
+
+int vfgs_hip_get_chroma_mix(int c, int out[4])
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (c < 1 || c > 2 || !out) return fail(37, "vfgs_hip_get_chroma_mix: component %d (1 = Cb, 2 = Cr)", c);
+	for (int i = 0; i < 4; i++) out[i] = g_mix[c - 1][i];
+	return 0;
+}
+
 int vfgs_hip_declare_frame(const void* Y, const void* U, const void* V, unsigned width, unsigned height, unsigned stride, unsigned cstride)
 {
 	std::lock_guard<std::mutex> g(g_mu);
@@ -2501,6 +2578,7 @@ void vfgs_hip_reset_state(void)
 	s.ymin = s.cmin = 0;
 	s.ymax = s.cmax = 255;
 	s.csubx = s.csuby = 2;
+	memset(g_mix, 0, sizeof g_mix);
 	s.lfsr.reseed(0xdeadbeefu);
 	s.seed_epoch++;
 	s.rnd = s.rnd_up = s.line_rnd = s.line_rnd_up = 0;

@@ -215,17 +215,21 @@ __device__ __forceinline__ uint32_t block_param(uint32_t v, uint32_t bank_off, i
 //   F = (l1 + 3 l0 + r0 + 2) >> 2 on true values becomes, in the P~ domain of the lane whose
 //   sample is filtered,  F~ = (a~ + 3 b~ + rel * c~ + (s > 0 ? 2 : 1)) >> 2  with rel = s * s'
 //   the relative sign of the two blocks: for s = -1, -((-A + 2) >> 2) == (A + 1) >> 2.
-template <int DEPTH, int BW, bool OVERLAP, bool ONE, bool ALIGN2, int NEG>
+//
+// MIX (chroma planes of grain_mix_kernel): the look-up index of a sample is not the sample but the luma / chroma mix `ix`, same layout
+// as `w` (mix_index below); only the LUT gathers read it.
+template <int DEPTH, int BW, bool OVERLAP, bool ONE, bool ALIGN2, int NEG, bool MIX = false>
 __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
                                             const RunParam<LaneMap<DEPTH == 8 ? 16 : 8, BW>::NR>& rp,
                                             const RunParam<LaneMap<DEPTH == 8 ? 16 : 8, BW>::NR>& up,
                                             const uint32_t lutb, const uint32_t rowoff, const uint32_t uprowoff, const int wcur, const int wup,
                                             const bool (&edge_on)[LaneMap<DEPTH == 8 ? 16 : 8, BW>::PAIR ? 1 : LaneMap<DEPTH == 8 ? 16 : 8, BW>::NE],
-                                            const bool first, const uint32_t lo2, const uint32_t hi2, const int pkshift)
+                                            const bool first, const uint32_t lo2, const uint32_t hi2, const int pkshift, const uint32_t (&ix)[4])
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
 	using M = LaneMap<NS, BW>;
 	constexpr int NR = M::NR, NQ = M::NQ;
+	auto index_dword = [&](int d) { return MIX ? ix[d] : w[d]; };
 	// 8-bit one-pattern form: int16 bank + table of scale bytes (vfgs_layout.h "packed 16-bit form"); pkshift = the scale shift
 	constexpr bool PK = DEPTH == 8 && ONE && kPk16;
 	static_assert(!(PK && M::PAIR), "lane pairs are 10-bit lanes");
@@ -252,7 +256,7 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 #pragma unroll
 		for (int q = 0; q < NQ; q++)
 		{
-			const uint32_t v = w[q];
+			const uint32_t v = index_dword(q);
 			const uint32_t s0 = lut[v & 0xffu], s1 = lut[(v >> 8) & 0xffu], s2 = lut[(v >> 16) & 0xffu], s3 = lut[v >> 24];
 			S[2 * q] = s0 | (s1 << 16);
 			S[2 * q + 1] = s2 | (s3 << 16);
@@ -312,7 +316,7 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 #pragma unroll
 			for (int h = 0; h < 2; h++)
 			{
-				const uint32_t idx = (w[2 * q + h] & 0x03fc03fcu) | k2;
+				const uint32_t idx = (index_dword(2 * q + h) & 0x03fc03fcu) | k2;
 				e[4 * q + 2 * h]     = *(const uint32_t*)(lds + (idx & 0xffffu));
 				e[4 * q + 2 * h + 1] = *(const uint32_t*)(lds + (idx >> 16));
 			}
@@ -320,7 +324,7 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 		else if (PK)
 		{
 			// (overlap lines of the packed 16-bit form: the scale byte itself)
-			const uint32_t v = w[q];
+			const uint32_t v = index_dword(q);
 			const uint8_t* lut = lds + (lutb & 0xffffu);
 			e[4 * q + 0] = lut[v & 0xffu];
 			e[4 * q + 1] = lut[(v >> 8) & 0xffu];
@@ -329,7 +333,7 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 		}
 		else
 		{
-			const uint32_t v = w[q], k1 = k2 & 0xffffu;
+			const uint32_t v = index_dword(q), k1 = k2 & 0xffffu;
 			e[4 * q + 0] = *(const uint32_t*)(lds + (((v << 2) & 0x3fcu) | k1));
 			e[4 * q + 1] = *(const uint32_t*)(lds + (((v >> 6) & 0x3fcu) | k1));
 			e[4 * q + 2] = *(const uint32_t*)(lds + (((v >> 14) & 0x3fcu) | k1));
@@ -498,6 +502,72 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 
 
 // ---------------------------------------------------------------------------------------
+// Luma / chroma mix of the look-up index (AFGS1 cb_mult / cb_luma_mult / cb_offset).
+//
+// One memory unit of a chroma row (c: 16 bytes) and the luma above it (l: 16 x SUBX bytes of luma row cy * suby) -> the unit's index
+// dwords m, in the sample layout:  m = clip(((avgL * lm + C * cm) >> 6) + off, 0, 2^depth - 1), avgL = the rounded mean of the two luma
+// samples over a horizontally subsampled chroma sample.  32-bit arithmetic per sample: L * lm + C * cm needs 8 + 8 + 1 bits at 8 bit and
+// 16 + 8 + 1 with a 16-bit container that holds anything, so nothing is packed; both products fit the 24-bit multiplier
+// (65535 x 128 < 2^23).  nv = index of the row's last luma sample (width - 1) relative to the unit's first: behind it the second sample
+// of a pair is the row's last one (lw1), which only the lanes at a row's end see.
+template <int DEPTH, int SUBX>
+__device__ __forceinline__ void mix_index(const uint32_t (&c)[4], uint32_t (&l)[4 * SUBX], const int lm, const int cm, const int off,
+                                          const int nv, const uint32_t lw1, uint32_t (&m)[4])
+{
+	constexpr int NS = DEPTH == 8 ? 16 : 8;
+	constexpr int MAXV = (1 << DEPTH) - 1;
+	if constexpr (SUBX == 2)
+	{
+		if (nv < 2 * NS - 1)
+		{
+#pragma unroll
+			for (int j = 0; j < NS; j++)
+			{
+				if (2 * j + 1 <= nv) continue;
+				if (DEPTH > 8) l[j] = (l[j] & 0xffffu) | (lw1 << 16);
+				else l[j / 2] = (l[j / 2] & ~(0xff00u << (16 * (j % 2)))) | (lw1 << (16 * (j % 2) + 8));
+			}
+		}
+	}
+	auto one = [&](uint32_t L, uint32_t C) {
+		const int v = ((__mul24((int)L, lm) + __mul24((int)C, cm)) >> 6) + off;
+		return (uint32_t)min(max(v, 0), MAXV);
+	};
+#pragma unroll
+	for (int d = 0; d < 4; d++)
+	{
+		if (DEPTH > 8)
+		{
+			uint32_t r[2];
+#pragma unroll
+			for (int h = 0; h < 2; h++)
+			{
+				const uint32_t C = h ? c[d] >> 16 : c[d] & 0xffffu;
+				uint32_t L;
+				if (SUBX == 2) { const uint32_t x = l[(2 * d + h) % (4 * SUBX)]; L = ((x & 0xffffu) + (x >> 16) + 1) >> 1; }
+				else L = h ? l[d] >> 16 : l[d] & 0xffffu;
+				r[h] = one(L, C);
+			}
+			m[d] = r[0] | (r[1] << 16);
+		}
+		else
+		{
+			uint32_t r[4];
+#pragma unroll
+			for (int i = 0; i < 4; i++)
+			{
+				const uint32_t C = (c[d] >> (8 * i)) & 0xffu;
+				uint32_t L;
+				if (SUBX == 2) { const uint32_t x = l[(2 * d + i / 2) % (4 * SUBX)] >> (16 * (i % 2)); L = ((x & 0xffu) + ((x >> 8) & 0xffu) + 1) >> 1; }
+				else L = (l[d] >> (8 * i)) & 0xffu;
+				r[i] = one(L, C);
+			}
+			m[d] = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------
 // memory helpers
 
 template <int AUX>
@@ -565,7 +635,11 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //   * OUT8 (10-bit source, 8-bit destination, yuv.c:216-258): out8 = (v + 2) >> 2 is applied to a lane's results, which
 //     halves them (DW = 2 dwords per unit); everything behind the computation -- rotation back, stores, descriptors -- works
 //     on those halves with the destination's own pitches.
-template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST>
+//   * MIX (chroma planes of grain_mix_kernel): a position also loads the 16 x SUBX bytes of luma row cy * SUBY that lie over a
+//     lane's chroma unit -- same descriptors-per-group scheme, so they are 16-byte coalesced and range-checked against the luma row, and
+//     issued with the position's own sample loads: they are part of the ring, which is two sets deep here -- forms the index dwords in
+//     the unit's layout (mix_index) and sends them through the same lane shift as the samples.
+template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
 {
@@ -585,12 +659,13 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	constexpr int BPS = M::PAIR ? 32 : 64 * M::BPL;      // grain blocks a position advances by
 	// positions per group = register sets of the ring = how many positions behind its load a position is stored (vfgs_layout.h)
 	// (narrow one-pattern planes at 10 bit -- rows of one or two positions: the chroma of 1080p -- walk with a ring of their own depth: vfgs_layout.h)
-	constexpr int NU = (DEPTH > 8 && ONE && NARROW != 0) ? VFGS_RING_NARROW10 : ring_depth<DEPTH, ONE>();
+	constexpr int NU = MIX ? 2 : ((DEPTH > 8 && ONE && NARROW != 0) ? VFGS_RING_NARROW10 : ring_depth<DEPTH, ONE>());
 	constexpr int GPP = kTileBlocks / (NU * BPS);        // groups per part of a row (a part = kTileBlocks blocks = one parameter table)
 	static_assert(GPP * NU * BPS == kTileBlocks, "a part is a whole number of groups");
 	constexpr uint32_t PT_CUR = IMG_BYTES, PT_UP = IMG_BYTES + kParamTableBytes;
 	static_assert(IMG_BYTES % 16 == 0, "table image in whole 16-byte units");
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
+	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
@@ -702,11 +777,36 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	auto left = [&](int g) { const uint32_t o = (uint32_t)g * GB; return o < pd.rowbytes ? min(pd.rowbytes - o, GB) : 0u; };
 	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD, rb = OUT8 ? pd.drowbytes : pd.rowbytes; return o < rb ? min(rb - o, GBD) : 0u; };
 	uint32_t w[NU][4];
+	// MIX: the luma over my chroma units (row cy * SUBY of the luma plane, SUBX units per chroma unit), in the ring with them
+	constexpr int LQ = MIX ? SUBX : 1;
+	const PlaneDesc& pl = a.pd[0];
+	const uint8_t* lbase = MIX ? (a.listed ? ft.src[0][f] : a.src[0] + (uint64_t)f * pl.fpitch) : nullptr;
+	auto lrow_off = [&](int k) { return (uint32_t)(((base + RSTR * k) * SUBY - a.y0) * (int)pl.pitch); };
+	uint32_t lw[MIX ? NU : 1][4 * LQ];
+	auto load_luma = [&](const __amdgpu_buffer_rsrc_t rs, const int u) {
+#pragma unroll
+		for (int i = 0; i < LQ; i++)
+		{
+			const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 * LQ + i * 16, 0, 0);
+			lw[u][4 * i] = t.x; lw[u][4 * i + 1] = t.y; lw[u][4 * i + 2] = t.z; lw[u][4 * i + 3] = t.w;
+		}
+	};
 	if constexpr (NARROW == 0)
 	{
 		const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(sbase + (k0 < k1 ? row_off(k0) : 0u), k0 < k1 ? left(0) : 0u);
 #pragma unroll
 		for (int u = 0; u < NU; u++) load_seg<LDA>(rs0, lane16 + u * UB, 0, w[u]);
+		if constexpr (MIX)
+		{
+#pragma unroll
+			for (int u = 0; u < NU; u++)
+			{
+				// (a descriptor per position: the position's step is twice 1 KiB at 4:2:x and need not fit the immediate offset)
+				const uint32_t o = (uint32_t)u * (UB * LQ);
+				const bool on = k0 < k1 && o < pl.rowbytes;
+				load_luma(make_rsrc(lbase + (on ? lrow_off(k0) + o : 0u), on ? min(pl.rowbytes - o, UB * LQ) : 0u), u);
+			}
+		}
 	}
 	else
 	{
@@ -771,6 +871,10 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 
 	// ---- the walk ----------------------------------------------------------------------------------------------------
 	uint32_t carry[4] = {0, 0, 0, 0};      // in lane 0: the last K dwords of lane 63 of the previous position of the row
+	uint32_t mcarry[4] = {0, 0, 0, 0};     // MIX: the same for the index dwords
+	const int mixc = comp == 2 ? 1 : 0;
+	const int mix_lm = MIX ? a.mix[mixc][0] : 0, mix_cm = MIX ? a.mix[mixc][1] : 0, mix_off = MIX ? a.mix[mixc][2] : 0;
+	const bool mix_on = MIX && a.mix[mixc][3] != 0;      // (a component without a mix of its own keeps the sample as its index)
 	uint32_t outp[DW] = {};                // the previous position's units: dwords KD.. of its lanes (the first DW - KD dwords of a unit)
 	uint32_t tp[KD > 0 ? KD : 1] = {};     // ... and the first KD dwords its lanes computed: they belong one lane down
 	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);     // where the previous GROUP's last position goes
@@ -827,13 +931,13 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 					{
 #pragma unroll
 						for (int rr = 0; rr < NR; rr++) up.pa[rr] = *(const uint32_t*)(pe + PT_UP + (p * BPS + rr) * 4) + pairoff;
-						grain_unit<DEPTH, BW, true, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, wc_, wu_, edge_on, first, lo2, hi2, a.pk_shift);
+						grain_unit<DEPTH, BW, true, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, wc_, wu_, edge_on, first, lo2, hi2, a.pk_shift, t);
 					}
 					else
 					{
 #pragma unroll
 						for (int rr = 0; rr < NR; rr++) up.pa[rr] = 0u;
-						grain_unit<DEPTH, BW, false, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, 0, 0, edge_on, first, lo2, hi2, a.pk_shift);
+						grain_unit<DEPTH, BW, false, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, 0, 0, edge_on, first, lo2, hi2, a.pk_shift, t);
 					}
 				}
 				uint32_t o[DW];
@@ -866,6 +970,15 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 		const uint32_t rowoff = (uint32_t)j * RS, uprowoff = (uint32_t)(RPB + j) * RS;
 		const int wc_ = jrow == 0 ? (SUBY > 1 ? 20 : 12) : 24, wu_ = jrow == 0 ? (SUBY > 1 ? 20 : 24) : 12;
 		const uint32_t ro = row_off(k), rod = row_offd(k);
+		// MIX: the row's last luma sample, the partner of every pair behind it (the lanes at the row's end only)
+		uint32_t lw1 = 0;
+		const uint32_t lro = MIX ? lrow_off(k) : 0u;
+		if constexpr (MIX && SUBX == 2)
+		{
+			const __amdgpu_buffer_rsrc_t lrs = make_rsrc(lbase + lro, pl.rowbytes);
+			const uint32_t at = (uint32_t)(a.mix_lw - 1) * SZ;
+			lw1 = SZ == 2 ? (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(lrs, at, 0, 0) : (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(lrs, at, 0, 0);
+		}
 		for (int g = g_lo; g < g_hi; g++)
 		{
 			// the group after this one (this row's next, or the next row's first): what the four refills fetch
@@ -883,6 +996,25 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				const bool firsts = u == 0 && g == 0;                    // first position of the row
 				// assemble my 16 bytes: the last K dwords of the unit of the lane before me, the first 4 - K of mine
 				uint32_t t[4];
+				uint32_t ti[4] = {};
+				if constexpr (MIX)
+				{
+					// index dwords of my memory unit, then the same lane shift as the samples
+					uint32_t mi[4];
+					if (mix_on)
+						mix_index<DEPTH, SUBX>(w[u], lw[u], mix_lm, mix_cm, mix_off, a.mix_lw - 1 - (((NU * g + u) * 64 + lane) * NS * SUBX), lw1, mi);
+					else
+					{
+#pragma unroll
+						for (int d = 0; d < 4; d++) mi[d] = w[u][d];
+					}
+#pragma unroll
+					for (int d = 0; d < K; d++) ti[d] = lane_up(firsts ? 0u : mcarry[d], mi[4 - K + d]);
+#pragma unroll
+					for (int d = 0; d < K; d++) mcarry[d] = rot_up(mi[4 - K + d]);
+#pragma unroll
+					for (int d = K; d < 4; d++) ti[d] = mi[d - K];
+				}
 #pragma unroll
 				for (int d = 0; d < K; d++) t[d] = lane_up(firsts ? 0u : carry[d], w[u][4 - K + d]);   // (in front of a row there is nothing)
 #pragma unroll
@@ -893,6 +1025,12 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				for (int d = K; d < 4; d++) asm volatile("v_mov_b32 %0, %1" : "=v"(t[d]) : "v"(w[u][d - K]));
 				// the registers are free: refill them with the position four steps ahead
 				load_seg<LDA>(nsrc, lane16 + u * UB, 0, w[u]);
+				if constexpr (MIX)
+				{
+					const uint32_t o = (uint32_t)(ng * NU + u) * (UB * LQ);
+					const bool on = nvalid && o < pl.rowbytes;
+					load_luma(make_rsrc(lbase + (on ? (lastg ? lrow_off(k + 1) : lro) + o : 0u), on ? min(pl.rowbytes - o, UB * LQ) : 0u), u);
+				}
 				if (NU * g + u < tsegs)
 				{
 					bool edge_on[NEF];
@@ -911,7 +1049,10 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 					for (int rr = 0; rr < NR; rr++) rp.pa[rr] = *(const uint32_t*)(pe + PT_CUR + (u * BPS + rr) * 4) + pairoff;
 #pragma unroll
 					for (int rr = 0; rr < NR; rr++) up.pa[rr] = OV ? *(const uint32_t*)(pe + PT_UP + (u * BPS + rr) * 4) + pairoff : 0u;
-					grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, a.pk_shift);
+					if constexpr (MIX)
+						grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG, true>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, a.pk_shift, ti);
+					else
+						grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, a.pk_shift, t);
 				}
 				uint32_t o[DW];
 				results(t, o);
@@ -1046,8 +1187,59 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 	}
 }
 
+// The kernels of the luma / chroma mix (KernelArgs::mix_kernel): all-one-pattern images only (AFGS1), the grid and the
+// workgroup numbering of grain_rw_kernel.  Luma workgroups are grain_rw_kernel's; chroma workgroups walk every row position by position
+// (no narrow-row form) with the luma over it in their ring.  KernelArgs::mix_planes switches the workgroups of one plane type off: an
+// in-place call is two launches on its stream, chroma first -- it reads luma as it is before this call -- then luma.  Four workgroups per
+// CU at either depth (128 registers; the LDS allocation says the same).
+template <int DEPTH, int CSUBX, int CSUBY, bool OUT8, bool WIDE>
+__global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kernel(const KernelArgs a, const FrameTable ft)
+{
+	constexpr ImageLayout L = image_layout(CSUBX, CSUBY, true, true, DEPTH == 8);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[mix_lds_allocation(L.lds_bytes + kParamBytes)];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	if (r < a.pd[0].wgs)
+	{
+		if (a.mix_planes & 1) return;
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, true, L.y_neg, 0, OUT8, WIDE, false>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	}
+	else
+	{
+		if (a.mix_planes & 2) return;
+		// Cb and Cr of the same rows read the same luma: their workgroups are numbered eight of Cb, the same eight of Cr, ... -- next to each
+		// other in time and (workgroups are dealt out to the eight XCDs in turn) on the same XCD, so that the second reader finds the luma in
+		// that XCD's L2 (the luma loads are ordinary loads, not nontemporal ones like the sample loads)
+		r -= a.pd[0].wgs;
+		const int n = a.pd[1].wgs, full = n & ~7;
+		int comp;
+		if (r < 2 * full) { comp = 1 + ((r >> 3) & 1); r = ((r >> 4) << 3) | (r & 7); }
+		else { r -= 2 * full; comp = 1 + (r >= n - full); r = full + (comp == 2 ? r - (n - full) : r); }
+		run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, true, L.c_neg, 0, OUT8, WIDE, false, true>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+	}
+}
+
 // ---------------------------------------------------------------------------------------
 // host-side launcher (called from vfgs_host.cpp)
+
+template <int DEPTH, int CSUBX, int CSUBY, bool OUT8>
+static hipError_t launch_mix(const KernelArgs& a, const FrameTable& ft, bool wide, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts);
+	if (wide)
+	{
+		// (rows walked in parts have all-one-pattern images at 4:2:0 and 4:4:4 only: launch_form)
+		if constexpr (CSUBX == CSUBY) hipLaunchKernelGGL((grain_mix_kernel<DEPTH, CSUBX, CSUBY, OUT8, true>), g, dim3(kWavesPerWG * 64), 0, stream, a, ft);
+		else return hipErrorInvalidValue;
+	}
+	else
+		hipLaunchKernelGGL((grain_mix_kernel<DEPTH, CSUBX, CSUBY, OUT8, false>), g, dim3(kWavesPerWG * 64), 0, stream, a, ft);
+	return hipGetLastError();
+}
 
 template <int DEPTH, int CSUBX, int CSUBY, bool OUT8, bool ONEY, bool ONEC, bool WIDE, bool PERSIST>
 static hipError_t launch_t(const KernelArgs& a, const FrameTable& ft, int grid, hipStream_t stream)
@@ -1101,6 +1293,19 @@ static hipError_t launch_form(const KernelArgs& a, const FrameTable& ft, bool on
 template <int D>
 static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
 {
+	if (a.mix_kernel)
+	{
+		if (!oney || !onec || persist) return hipErrorInvalidValue;
+#define VFGS_CASE(X, Y)                                                                                  \
+	if (csubx == X && csuby == Y)                                                                        \
+	{                                                                                                    \
+		if constexpr (D == 10) { if (out8) return launch_mix<D, X, Y, true>(a, ft, wide, grid, stream); } \
+		return launch_mix<D, X, Y, false>(a, ft, wide, grid, stream);                                     \
+	}
+		VFGS_CASE(2, 2) VFGS_CASE(2, 1) VFGS_CASE(1, 1) VFGS_CASE(1, 2)
+#undef VFGS_CASE
+		return hipErrorInvalidValue;
+	}
 #define VFGS_CASE(X, Y)                                                                                                     \
 	if (csubx == X && csuby == Y)                                                                                           \
 	{                                                                                                                       \
@@ -1125,6 +1330,7 @@ hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable& ft, int csubx,
 hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
 {
 	if ((out8 && depth != 10) || wide != (a.nblk > kTileBlocks)) return hipErrorInvalidValue;
+	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return hipErrorInvalidValue;
 	if ((a.listed != 0) != (list != nullptr) || (list && a.nframes > kListFrames)) return hipErrorInvalidValue;
 	static const FrameTable no_list{};
 	const FrameTable& ft = list ? *list : no_list;

@@ -104,6 +104,15 @@ constexpr int lds_allocation(const bool depth10, const bool one_y, const bool on
 	return need > next ? need : (target < 65536 ? target : 65536);
 }
 
+// The kernels of the luma / chroma mix (grain_mix_kernel): four workgroups per CU at either depth -- their chroma waves hold the luma over
+// their samples in the ring as well and are compiled for 128 registers -- and an LDS allocation that says the same.
+constexpr int kMixWgPerCU = 4;
+constexpr int mix_lds_allocation(const int need)
+{
+	const int target = (kLdsPerCU / kMixWgPerCU) & ~2047;
+	return need > target ? need : target;
+}
+
 // Device image of everything the kernel looks up: one sub-image per plane type (luma; chroma) -- or per chroma
 // component -- and a workgroup (which works on ONE plane) copies the sub-image of its plane to LDS offset 0.
 //
@@ -235,6 +244,11 @@ struct KernelArgs {
 	int persist_step_f, persist_step_r;   // ... and P = persist_step_f * pd[0].wgs + persist_step_r: what a workgroup advances by
 	int pk_shift;             // 8-bit one-pattern forms (packed 16-bit form, above): the scale shift of vfgs_hw.c:263, 8..13
 	uint32_t lo2[2], hi2[2];  // clip bounds in sample units (I_min<<bs ...) in both halves of a dword, per plane type (vfgs_hw.c:264-267)
+	// Luma / chroma mix of the chroma look-up index (vfgs_hip_set_chroma_mix; all zero = the kernels and the launch of always)
+	int mix_kernel;           // 1: grain_mix_kernel serves the launch (all-one-pattern images only)
+	int mix_planes;           // ... bit 0: its luma workgroups do nothing, bit 1: its chroma workgroups do nothing (the two launches of an in-place call)
+	int mix_lw;               // ... luma width of the call in samples (the last luma sample of a row pairs with itself)
+	int mix[2][4];            // ... Cb, Cr: { luma_mult, chroma_mult, offset << (depth - 8), active }
 };
 
 }  // namespace vfgs

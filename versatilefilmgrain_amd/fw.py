@@ -14,7 +14,7 @@ SEI_MAX_MODEL_VALUES = 6   # vfgs_fw.h:49
 
 EXPORTS = ["vfgs_init_sei", "vfgs_init_afgs1", "vfgs_hip_generate_patterns", "vfgs_hip_get_pattern",
            "vfgs_hip_cfg_defaults", "vfgs_hip_cfg_read", "vfgs_hip_cfg_check", "vfgs_hip_cfg_adjust_chroma",
-           "vfgs_hip_cfg_apply_gain", "vfgs_hip_cfg_program"]
+           "vfgs_hip_cfg_apply_gain", "vfgs_hip_cfg_program", "vfgs_hip_afgs1_chroma_mix"]
 
 
 class FgsSei(C.Structure):   # vfgs_fw.h:51-60
@@ -119,6 +119,8 @@ def _lib():
         lib.vfgs_hip_cfg_apply_gain.restype = None
         lib.vfgs_hip_cfg_program.argtypes = [C.POINTER(Cfg)]
         lib.vfgs_hip_cfg_program.restype = None
+        lib.vfgs_hip_afgs1_chroma_mix.argtypes = [C.c_int]
+        lib.vfgs_hip_afgs1_chroma_mix.restype = None
         lib._fw_typed = True
     return lib
 
@@ -137,6 +139,11 @@ def init_sei(cfg: FgsSei) -> None:
 
 def init_afgs1(cfg: FgsAfgs1) -> None:
     _lib().vfgs_init_afgs1(C.byref(cfg))
+
+
+def afgs1_chroma_mix(enable: bool) -> None:
+    """Process-wide: init_afgs1 also programs the luma / chroma mix of cb_mult, cb_luma_mult, cb_offset (include/vfgs_hip_fw.h)."""
+    _lib().vfgs_hip_afgs1_chroma_mix(1 if enable else 0)
 
 
 def init(cfg) -> None:

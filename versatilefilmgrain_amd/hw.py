@@ -128,6 +128,10 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_host_free.argtypes = [vp]
     lib.vfgs_hip_host_free.restype = None
     lib.vfgs_hip_last_launch_info.argtypes = [C.POINTER(LaunchInfo)]
+    lib.vfgs_hip_set_chroma_mix.argtypes = [i, i, i, i]
+    lib.vfgs_hip_clear_chroma_mix.argtypes = []
+    lib.vfgs_hip_clear_chroma_mix.restype = None
+    lib.vfgs_hip_get_chroma_mix.argtypes = [i, C.POINTER(i)]
     # a library built by a developer tool with tuning / ablation knobs may compute something else by design: only on request
     if lib.vfgs_hip_dev_build() and not os.environ.get("VFGS_ALLOW_DEV_BUILD"):
         raise VfgsHipError(f"{path} is a developer build (tuning / ablation knobs); set VFGS_ALLOW_DEV_BUILD=1 to load it anyway")
@@ -163,6 +167,7 @@ EXPORTS = [
     "vfgs_hip_dev_build", "vfgs_hip_init_devices", "vfgs_hip_overlap_begin", "vfgs_hip_overlap_end", "vfgs_hip_get_stream_stats", "vfgs_hip_line_lookahead", "vfgs_hip_declare_frame",
     "vfgs_hip_get_stripe_stream_stats", "vfgs_hip_lfsr_segments",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
+    "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix",
 ]
 
 
@@ -278,6 +283,19 @@ class VfgsHip:
         out = (C.c_int * 8)()
         self.lib.vfgs_hip_get_params(out)
         return dict(zip(("scale_shift", "bs", "ymin", "ymax", "cmin", "cmax", "csubx", "csuby"), out))
+
+    def set_chroma_mix(self, c, luma_mult, chroma_mult, offset):
+        """Luma / chroma mix of component c's (1 = Cb, 2 = Cr) look-up index (include/vfgs_hip.h)."""
+        self._ck(self.lib.vfgs_hip_set_chroma_mix(c, luma_mult, chroma_mult, offset))
+
+    def clear_chroma_mix(self):
+        self.lib.vfgs_hip_clear_chroma_mix()
+
+    def chroma_mix(self, c):
+        """(luma_mult, chroma_mult, offset, active) of component c."""
+        out = (C.c_int * 4)()
+        self._ck(self.lib.vfgs_hip_get_chroma_mix(c, out))
+        return tuple(out)
 
     def line_lookahead(self, enable):
         self.lib.vfgs_hip_line_lookahead(1 if enable else 0)
