@@ -49,7 +49,10 @@ void vfgs_set_pattern_lut(int c, unsigned char lut[]);
 void vfgs_set_seed(unsigned int seed);
 /* vfgs_hw.h:57 / vfgs_hw.c:346-350 -- shift in 2..7. */
 void vfgs_set_scale_shift(int shift);
-/* vfgs_hw.h:58 / vfgs_hw.c:352-362 -- 8 or 10. */
+/* vfgs_hw.h:58 / vfgs_hw.c:352-362 -- 8, 10 or 12 (vfgs_hip_supports_depth).  The reference stops at 10 (vfgs_hw.c:354); depth 12 is its
+ * formulas with bs = depth - 8 = 4, quirks included: samples are uint16, intensity = (I >> 4) & 0xff (a container value above 4095
+ * wraps), clip limits I_min << 4 and I_max << 4 (full range: 4080, not 4095), scale_shift as stored = shift + 2; the seed registers
+ * and the LFSR stream do not depend on the depth. */
 void vfgs_set_depth(int depth);
 /* vfgs_hw.h:59 / vfgs_hw.c:364-380 */
 void vfgs_set_legal_range(int legal);
@@ -108,9 +111,10 @@ void vfgs_hip_reset_state(void);
  * luma_mult, chroma_mult: units of 1/64, -128..127; offset: 8-bit code values, -256..255.  (0, 64, 0) is neutral.
  * Nothing else changes: the grain added to luma, the seed registers, clipping.  Every processing entry point of this
  * header honours an active mix, in place (the chroma planes are then computed in a launch of their own in front of luma's)
- * and out of place, with three exceptions that REFUSE with error 38 and change nothing: a programmed model that needs a
+ * and out of place, with four exceptions that REFUSE with error 38 and change nothing: a programmed model that needs a
  * general-form pattern bank (a pattern LUT that selects more than one pattern; a one-pattern model wider than 8192 samples
- * at 4:2:2 or 4:4:0) -- the kernels of the mix exist for the one-pattern banks of the AFGS1 models --, and
+ * at 4:2:2 or 4:4:0) -- the kernels of the mix exist for the one-pattern banks of the AFGS1 models --, depth 12 -- they
+ * exist at 8 and 10 bit; every processing call refuses while both hold --, and
  * vfgs_add_grain_stripe / vfgs_hip_add_grain_frames_host while several devices are set (vfgs_hip_init_devices).  While a
  * mix is active vfgs_add_grain_line computes line by line (no look-ahead).
  * set: 0, or error 37 (component or range) with nothing changed.  get: out[4] = { luma_mult, chroma_mult, offset, active }. */
@@ -166,7 +170,8 @@ int vfgs_hip_add_grain_copy_dev(const void* sY, const void* sU, const void* sV, 
 
 /* The same with the output narrowed to 8 bit in the store: dst sample = (uint8)((v + 2) >> 2),
  * i.e. the reference CLI's `--outdepth 8` step yuv_to_8bit (yuv.c:216-258, called at
- * vfgs_main.c:787-788) fused into the kernel.  Needs vfgs_set_depth(10).  Source planes hold
+ * vfgs_main.c:787-788) fused into the kernel; at depth 12 (uint8)((v + 8) >> 4), the same rounding (the full-range
+ * maximum 4080 gives 255).  Needs vfgs_set_depth(10) or (12); error 16 at depth 8.  Source planes hold
  * uint16 samples (strides in samples), destination planes uint8 samples with their own strides
  * and frame pitches (multiples of 16).  Halves the write traffic of the path. */
 int vfgs_hip_add_grain_copy8_dev(const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV,
@@ -186,7 +191,7 @@ int vfgs_hip_add_grain_copy8_dev(const void* sY, const void* sU, const void* sV,
  * same plane listed twice, or two whose rows overlap -- and, in the _copy forms, a source plane that shares bytes with the
  * destination of ANOTHER frame (consecutive calls would read it grained or not, deterministically; one launch would not).
  * _copy: out of place, src[f] -> dst[f], same geometry (a plane of src[f] may BE the plane of dst[f]: in place);
- * _copy8: 10-bit source, 8-bit destination as vfgs_hip_add_grain_copy8_dev.  A refused call changes nothing. */
+ * _copy8: 10- or 12-bit source, 8-bit destination as vfgs_hip_add_grain_copy8_dev.  A refused call changes nothing. */
 typedef struct vfgs_hip_frame_ptrs { void* Y; void* U; void* V; } vfgs_hip_frame_ptrs;
 int vfgs_hip_add_grain_frame_list_dev(const vfgs_hip_frame_ptrs* frames, unsigned nframes, unsigned width, unsigned height,
                                       unsigned stride, unsigned cstride, void* stream);
@@ -257,6 +262,10 @@ int vfgs_hip_overlap_end(void* stream);
  * 0 or an error code. */
 int vfgs_hip_init_devices(const int* devices, int n);
 
+/* 1 if vfgs_set_depth(depth) is accepted (8, 10, 12), else 0: a way to ask that does not abort like the void drop-in call.
+ * Host only, no GPU needed. */
+int vfgs_hip_supports_depth(int depth);
+
 /* 1 if this library was built by a developer tool with tuning or ablation knobs (its output may be wrong by design),
  * 0 for the product build.  versatilefilmgrain_amd/build.py only ever builds the latter. */
 int vfgs_hip_dev_build(void);
@@ -283,12 +292,12 @@ int vfgs_hip_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, c
  * vfgs_add_grain_line, the stripes it computes ahead -- including ones that are dropped later --, vfgs_add_grain_stripe,
  * vfgs_hip_add_grain_frames_host): after a walk through the line call the record describes such a stripe launch.  `kernel` is the instantiation's name as the
  * profiler prints it (e.g. "grain_rw_kernel<10,2,2,false,false,true,false,false>": depth, chroma subsampling
- * x / y, 8-bit destination of a 10-bit path, luma one-pattern form, chroma one-pattern form, rows walked in parts,
+ * x / y, 8-bit destination of a 10- or 12-bit path, luma one-pattern form, chroma one-pattern form, rows walked in parts,
  * persistent luma workgroups; with a chroma mix active "grain_mix_kernel<10,2,2,false,false>": depth, chroma subsampling x / y,
  * 8-bit destination, rows walked in parts -- an in-place call is two launches of it).  Returns 0, or -1 when nothing has been launched yet. */
 typedef struct vfgs_hip_launch_info {
 	int depth, csubx, csuby;          /* sample depth and chroma format the launch was compiled for */
-	int out8;                         /* 1: 10-bit source narrowed to 8 bit in the store */
+	int out8;                         /* 1: 10- or 12-bit source narrowed to 8 bit in the store */
 	int one_y, one_c;                 /* 1: one-pattern form of the luma / chroma table image */
 	int in_place;                     /* 1: destination planes == source planes */
 	int nframes;                      /* frames of the launch */
@@ -299,7 +308,7 @@ typedef struct vfgs_hip_launch_info {
 	int parts_per_row;                /* passes over the block-parameter table a row needs (1 up to 512 blocks = 8192 samples per row) */
 	int persistent_luma_workgroups;   /* 0, or the number of luma workgroups that share the launch's luma tasks (general-form luma of small pictures) */
 	int waves_per_workgroup;
-	int lds_bytes_per_workgroup;      /* LDS the kernel allocates: table image + block parameters (the 10-bit all-one-pattern kernels: padded to 40,960, four workgroups per CU) */
+	int lds_bytes_per_workgroup;      /* LDS the kernel allocates: table image + block parameters (the 10- and 12-bit all-one-pattern kernels: padded to 40,960, four workgroups per CU) */
 	unsigned long long launches;      /* grain launches of this process so far */
 	char kernel[96];
 	int listed;                       /* 1: the frames' plane pointers came as a list (vfgs_hip_add_grain_frame_list_*) */

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool: ONE BASELINE.json configuration on one MI355X, device-resident frames, in place.
-`python3 tools/bench_config.py --config 0..4 [--batch 8] [--steps 200]` prints one JSON line; run directly behind
+`python3 tools/bench_config.py --config 0..4 [--batch 8] [--steps 200] [--depth 12]` prints one JSON line; run directly behind
 `rocprofv3 --kernel-trace --stats -- python3 tools/bench_config.py ...` for the per-config kernel statistics
 kept under profiles/ (tools/gpu_profiles.sh)."""
 import argparse
@@ -40,6 +40,8 @@ CONFIGS = [  # BASELINE.json configs[i]: name, w, h, depth, (subx, suby), trace,
     ("16384x2160 10-bit 4:2:0 fgs_sei", 16384, 2160, 10, (2, 2), "fgs_sei_10_420", "grain_rw_kernel<10,2,2,false,false,true,true,false>"),
     # 16: one luma pattern over several chroma patterns at 4:2:0 (one-pattern luma, general-form chroma: 15 KB of LDS)
     ("3840x2160 10-bit 4:2:0 fgs_sei_ff_test6", 3840, 2160, 10, (2, 2), "fgs_sei_ff_test6_10_420", "grain_rw_kernel<10,2,2,false,true,false,false,false>"),
+    # 17: the all-one-pattern kernels with every plane of luma geometry at 10 bit (and, with --depth 12, at 12)
+    ("3840x2160 10-bit 4:4:4 fgs_afgs1_test1", 3840, 2160, 10, (1, 1), "fgs_afgs1_test1_10_444", "grain_rw_kernel<10,1,1,false,true,true,false,false>"),
 ]
 
 
@@ -53,7 +55,7 @@ def main():
                     help="uniform: random over the full code range (worst case for LUT / pattern divergence, SURVEY 8d); "
                          "ramp: smooth diagonal ramp + -4..+4 noise (natural-like, reported separately)")
     ap.add_argument("--mode", choices=["inplace", "copy", "copy8"], default="inplace",
-                    help="inplace (default); copy: out of place, same depth; copy8: 10-bit in, 8-bit out (the CLI's --outdepth 8 fused into the store)")
+                    help="inplace (default); copy: out of place, same depth; copy8: 10- or 12-bit in, 8-bit out (the CLI's --outdepth 8 fused into the store)")
     ap.add_argument("--overlap", action="store_true", help="time the calls inside one vfgs_hip_overlap_begin/_end region (independent frames, one per call)")
     ap.add_argument("--region-every", type=int, default=0, help="with --overlap: close and reopen the region every N calls (a join every N calls)")
     ap.add_argument("--streams", type=int, default=1, help="experiment: issue consecutive launches round-robin on this many streams (they may overlap)")
@@ -65,6 +67,8 @@ def main():
     ap.add_argument("--height", type=int, default=0, help="override the picture height (experiments)")
     ap.add_argument("--mix", default="", help="luma_mult,chroma_mult,offset: the same luma / chroma mix of the look-up index for Cb and Cr "
                                                 "(vfgs_hip_set_chroma_mix; one-pattern models, e.g. configs 3, 5, 7, 9)")
+    ap.add_argument("--depth", type=int, default=0, choices=[0, 12], help="12: replay the chosen 10-bit configuration's trace with its depth record replaced by 12 "
+                                                                           "(same bytes per frame as at 10 bit; the kernels are grain_rw_kernel<12,...>)")
     ap.add_argument("--stride", type=int, default=0, help="luma row pitch in samples (default: the width; chroma: stride / subx), inplace mode only (experiments)")
     args = ap.parse_args()
     name, w, hh, depth, (sx, sy), trace, kernel = CONFIGS[args.config]
@@ -73,11 +77,17 @@ def main():
         name += " [size %dx%d]" % (w, hh)
     if args.stride:
         name += " [stride %d]" % args.stride
+    records = T.load_trace(trace)
+    if args.depth == 12:
+        assert depth == 10, "--depth 12 replays a 10-bit configuration"
+        records = [(op, 12 if op == T.OP_DEPTH else a, b, p) for op, a, b, p in records]
+        depth = 12
+        name = name.replace("10-bit", "12-bit") + " [depth record 12]"
     import os
     if os.environ.get("VFGS_LIB"):
         hw.load(os.environ["VFGS_LIB"])      # a variant build (tools/gpu_variants.sh)
     h = hw.VfgsHip(device=0)
-    T.replay(h, T.load_trace(trace))
+    T.replay(h, records)
     if args.mix:
         for c in (1, 2):
             h.set_chroma_mix(c, *map(int, args.mix.split(",")))

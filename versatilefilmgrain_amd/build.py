@@ -61,9 +61,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     common = [hipcc(), "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function", f'-DVFGS_FW_TABLES_PATH="{FW_TABLES}"']
     if verbose:
         common.insert(1, "-Rpass-analysis=kernel-resource-usage")
-    # One object per translation unit, compiled side by side (110 -> 60 s).  The grain kernels are TWO units out of one source -- one code
-    # object per sample depth (vfgs_kernel.hip, launch_grain): a process works at one depth and never loads the other's kernels.
-    units = [(CSRC / "vfgs_kernel.hip", "vfgs_kernel_d10.o", ["-DVFGS_KERNEL_DEPTH=10"]), (CSRC / "vfgs_kernel.hip", "vfgs_kernel_d8.o", ["-DVFGS_KERNEL_DEPTH=8"])]
+    # One object per translation unit, compiled side by side (110 -> 60 s).  The grain kernels are THREE units out of one source -- one code
+    # object per sample depth (vfgs_kernel.hip, launch_grain): a process works at one depth and never loads the others' kernels.
+    units = [(CSRC / "vfgs_kernel.hip", f"vfgs_kernel_d{d}.o", [f"-DVFGS_KERNEL_DEPTH={d}"]) for d in (10, 12, 8)]
     units += [(src, src.stem + ".o", []) for src in SOURCES[1:]]
     with tempfile.TemporaryDirectory(prefix="vfgs_build_") as tmp:
         def compile_unit(u):

@@ -1173,7 +1173,8 @@ void build_tables(const State& s, uint8_t* img, const vfgs::ImageLayout& L, bool
 			const int sl = s.plut[c][i] >> 4;   // vfgs_hw.c:212
 			const uint32_t sel = sl < vfgs::kSlots ? (uint32_t)sl : 0x0cu;  // slot 8: the reference's all-zero bank
 			// scale pre-shifted so that (scale' * P + 2^15) >> 16 == round(scale * P, scale_shift) (vfgs_hw.c:263):
-			// the kernel reads the result's high half instead of shifting; <= 255 << 10 fits the 24-bit field
+			// the kernel reads the result's high half instead of shifting; the stored shift is shift + 6 - bs >= 4 (12 bit), so
+			// <= 255 << 12 < 2^23 fits the signed 24-bit field (ranges: vfgs_kernel.hip grain_unit "scale, add, clip")
 			const int sc = s.slut[c][i] << (16 - s.scale_shift);
 			lut[i] = (sel << 24) | ((uint32_t)sc & 0xffffffu);             // +scale table
 			if (!(c == 0 ? one_y : one_c)) lut[256 + i] = (sel << 24) | ((uint32_t)(-sc) & 0xffffffu);    // -scale table (general form only)
@@ -1334,7 +1335,7 @@ int check_geometry(const State& s, const void* dY, const void* dU, const void* d
 }
 
 // Core: launch the kernel over `nframes` frames, lines [part_y, part_y+part_h) of each.
-struct DstGeom {          // destination geometry when it differs from the source's (8-bit output of a 10-bit path)
+struct DstGeom {          // destination geometry when it differs from the source's (8-bit output of a 10- or 12-bit path)
 	bool out8 = false;
 	unsigned stride = 0, cstride = 0;
 	uint64_t ypitch = 0, cpitch = 0;
@@ -1356,7 +1357,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	else
 	{
 		const unsigned nb = (width + 15) / 16;
-		if (s.bs != 2) return fail(16, "8-bit output needs a 10-bit path (vfgs_set_depth(10))");
+		if (s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
 		if (dg.stride < nb * 16 || dg.cstride < nb * 16 / s.csubx) return fail(6, "destination stride too small");
 		if ((((uintptr_t)dY | (uintptr_t)dU | (uintptr_t)dV) & 15) || dg.stride % 16 || dg.cstride % 16 || (dg.ypitch | dg.cpitch) % 16)
 			return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
@@ -1394,6 +1395,8 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
 	const bool mix = mix_active();
+	if (mix && s.bs == 4)
+		return fail(38, "a chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit");
 	if (mix && !(form_one_y && form_one_c))
 		return fail(38, "a chroma mix is active and the programmed model needs a general-form pattern bank (%s rows): not supported", wide ? "wide" : "ordinary");
 	if (mix && &s != &g_states[0])
@@ -1501,9 +1504,9 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	// in memory order together); chroma keeps one workgroup per task behind them in the grid.
 	bool persist = false;
 	long grid = per_frame;
-	// (10 bit only: at 8 bit the general-form kernels are bound by their LDS instructions, and confining luma to P < all workgroup
+	// (10 and 12 bit -- the same bytes through the same LDS image -- only: at 8 bit the general-form kernels are bound by their LDS instructions, and confining luma to P < all workgroup
 	// slots costs them 7 %; at 10 bit 1080p gains 6 % at 32 and 64 frames per launch, 2160p nothing: profiles/r04_ab2_persistent_luma.log)
-	if (VFGS_PERSIST_MIN_TASKS > 0 && s.bs == 2 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
+	if (VFGS_PERSIST_MIN_TASKS > 0 && s.bs != 0 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
 	    (size_t)vfgs::kWavesPerWG * a.pd[0].rw_rpw * a.pd[0].rowbytes <= ((size_t)VFGS_PERSIST_MAX_WG_KB << 10))
 	{
 		const long tasks = (long)a.pd[0].wgs * nframes, slots = (long)s.cu_count * 4;     // (general form: four workgroups per CU)
@@ -2464,7 +2467,8 @@ void vfgs_set_depth(int depth)
 	S().gen++;
 	S().prog_gen++;
 	State& s = S();
-	if (depth != 8 && depth != 10) { fail(23, "vfgs_set_depth: %d", depth); die("depth must be 8 or 10 (vfgs_hw.c:354)"); }
+	// (the reference stops at 10, vfgs_hw.c:354; its formulas are written in bs = depth - 8 and hold at 12)
+	if (!vfgs_hip_supports_depth(depth)) { fail(23, "vfgs_set_depth: %d", depth); die("depth must be 8, 10 or 12 (vfgs_hw.c:354)"); }
 	if (s.bs != depth - 8) s.tables_dirty = true;
 	s.scale_shift += s.bs - (depth - 8);     // vfgs_hw.c:356-359
 	s.bs = depth - 8;
@@ -3022,6 +3026,11 @@ int vfgs_hip_timer_end(void* stream, float* elapsed_ms)
 	HIP_TRY(hipEventSynchronize(S().ev1));
 	HIP_TRY(hipEventElapsedTime(elapsed_ms, S().ev0, S().ev1));
 	return 0;
+}
+
+int vfgs_hip_supports_depth(int depth)
+{
+	return depth == 8 || depth == 10 || depth == 12;
 }
 
 int vfgs_hip_dev_build(void)

@@ -11,7 +11,7 @@
 // window of the block row above feeds the 2-line overlap.
 //
 // Work decomposition ("row walk"; one kernel family since round 4):
-//   * every lane moves 16 bytes per access (8 samples at 10 bit, 16 samples at 8 bit), one wave access = one line-aligned
+//   * every lane moves 16 bytes per access (8 samples at 10 and 12 bit, 16 samples at 8 bit), one wave access = one line-aligned
 //     1 KiB "position" of a row;
 //   * the lanes COMPUTE bytes shifted left of the block grid by half a block, so every block edge -- the only place where a
 //     sample depends on its horizontal neighbours -- lies inside a lane or between the two lanes of a pair: no halo, no
@@ -24,7 +24,7 @@
 //   * a component whose pattern LUT selects one slot for every intensity is served from a packed one-byte-per-sample bank
 //     (ONEY / ONEC kernels, vfgs_layout.h);
 //   * rows of more than 512 grain blocks (8192 luma samples) are walked in parts of 512 blocks, the parameter table refilled
-//     between the parts; the 8-bit output of a 10-bit path (yuv.c:216-258) is a narrowing in the store (OUT8 kernels);
+//     between the parts; the 8-bit output of a 10- or 12-bit path (yuv.c:216-258) is a narrowing in the store (OUT8 kernels);
 //   * the frames of a launch lie at a constant pitch behind the plane pointers of the arguments, or anywhere: then their plane
 //     pointers are a table IN the kernel arguments (FrameTable, vfgs_layout.h) and a workgroup reads its frame's with scalar loads.
 #include <hip/hip_runtime.h>
@@ -316,7 +316,19 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 #pragma unroll
 			for (int h = 0; h < 2; h++)
 			{
-				const uint32_t idx = (index_dword(2 * q + h) & 0x03fc03fcu) | k2;
+				// 10 bit: sample & 0x3fc IS 4 * intensity.  12 bit: the intensity sits in bits 11:4 of each half-word, two bits further
+				// up: one v_lshrrev_b32 for the pair in front of the same v_and_or_b32 (bits 3:2 of the upper sample land in bits 1:0
+				// of the upper half and bits 15:14 of the lower, all outside the mask) -- half a VOP2 instruction per sample more than
+				// at 10 bit, and no cheaper pair exists: a v_bfe_u32 per sample still needs its << 2
+				uint32_t sv = index_dword(2 * q + h);
+				if constexpr (DEPTH == 12)
+				{
+					// (opaque, so that the pair keeps ONE shift: where k2 is 0 -- the one-pattern form -- the compiler otherwise splits the
+					// pair first and shifts each half, four instructions for the two indices instead of three)
+					sv >>= 2;
+					asm("" : "+v"(sv));
+				}
+				const uint32_t idx = (sv & 0x03fc03fcu) | k2;
 				e[4 * q + 2 * h]     = *(const uint32_t*)(lds + (idx & 0xffffu));
 				e[4 * q + 2 * h + 1] = *(const uint32_t*)(lds + (idx >> 16));
 			}
@@ -454,6 +466,13 @@ __device__ __forceinline__ void grain_unit(const uint8_t* lds, uint32_t (&w)[4],
 	// scale, add, clip (vfgs_hw.c:263-267)
 	// round(scale * P, shift) (vfgs_hw.c:263) = (scale * 2^(16-shift) * P + 2^15) >> 16 exactly; the LUT holds
 	// scale * 2^(16-shift), so the shift is free: the pack below simply takes the high halves
+	// Ranges, at the widest case -- 12 bit, where the stored shift is 4..9 (vfgs_hw.c:349,356-359: shift + 6 - bs) and an entry reaches 255 << 12:
+	//   * entry: 255 << 12 = 1 044 480 < 2^23, so +entry and -entry fit the signed 24-bit operand of v_mad_i32_i24;
+	//   * |P|: a pattern byte is at most 128, the overlap blend (w_cur + w_up <= 40, >> 5) at most (128 * 40 + 16) >> 5 = 160, the 3-tap
+	//     edge filter on blended values at most (5 * 160 + 2) >> 2 = 200; 200 * 1 044 480 + 0x8000 = 208 928 768 < 2^31;
+	//   * the grain that comes out of the high half is at most 208 928 768 >> 16 = 3187 in magnitude; clip2 caps the sample at 0x7000 = 28 672
+	//     first, so the int16 sum lies in [-3188, 31 860]: inside int16 (at 10 bit the entry reaches 255 << 10 and the grain 797, at 8 bit
+	//     255 << 8 and 199).
 	// scaled grain of sample i, before the final >> 16: from the value itself where the edge filter may have changed it, straight
 	// from the pattern byte (one-pattern form, no overlap blend) everywhere else
 	auto edge_sample = [](int i) {
@@ -632,7 +651,7 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //   * rows of more than kTileBlocks blocks (WIDE kernels): the table holds one PART of
 //     the row (kTileBlocks blocks) at a time; all waves walk part 0 of their row, the workgroup refills the table for part 1
 //     between two barriers, and so on -- the ring of register sets simply runs on (the host gives such workgroups one row per wave);
-//   * OUT8 (10-bit source, 8-bit destination, yuv.c:216-258): out8 = (v + 2) >> 2 is applied to a lane's results, which
+//   * OUT8 (10- or 12-bit source, 8-bit destination, yuv.c:216-258): out8 = (v + 2) >> 2 (12 bit: (v + 8) >> 4) is applied to a lane's results, which
 //     halves them (DW = 2 dwords per unit); everything behind the computation -- rotation back, stores, descriptors -- works
 //     on those halves with the destination's own pitches.
 //   * MIX (chroma planes of grain_mix_kernel): a position also loads the 16 x SUBX bytes of luma row cy * SUBY that lie over a
@@ -653,7 +672,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	constexpr int K = M::SHIFT * SZ / 4;                 // dwords of a lane that lie in the memory unit before the lane's own
 	constexpr int DW = OUT8 ? 2 : 4;                     // dwords of a unit in the destination ...
 	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of a lane's result dwords belong to the unit before its own
-	static_assert(!OUT8 || (DEPTH == 10 && K % 2 == 0), "the narrowed destination exists for 10-bit sources");
+	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0), "the narrowed destination exists for 16-bit containers");
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LPB = M::PAIR ? 1 : M::BPL;            // blocks per lane step (PAIR: half a block, see idx0 below)
 	constexpr int BPS = M::PAIR ? 32 : 64 * M::BPL;      // grain blocks a position advances by
@@ -852,13 +871,14 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	auto rot_up = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x13c, 0xf, 0xf, false); };      // wave_ror:1: lane 0 <- lane 63
 	auto rot_down = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x134, 0xf, 0xf, false); };    // wave_rol:1: lane 63 <- lane 0
 	// a lane's results as they go to memory: the 4 dwords themselves, or narrowed to 8 bit (yuv_to_8bit, yuv.c:216-258:
-	// out8 = (v + 2) >> 2; both halves of a dword are <= 1023 + 2: no carry across them)
+	// out8 = (v + 2) >> 2 at 10 bit, in general (v + 2^(bs-1)) >> bs: (v + 8) >> 4 at 12 bit; both halves of a dword are <= (255 << bs) + 2^(bs-1)
+	// behind the clip: no carry across them, and the result is at most 255)
 	auto results = [](const uint32_t (&t)[4], uint32_t (&o)[DW]) {
 		if constexpr (OUT8)
 		{
 			uint32_t n[4];
 #pragma unroll
-			for (int d = 0; d < 4; d++) n[d] = ((t[d] + 0x00020002u) >> 2) & 0x00ff00ffu;
+			for (int d = 0; d < 4; d++) n[d] = ((t[d] + (0x00010001u << (DEPTH - 9))) >> (DEPTH - 8)) & 0x00ff00ffu;
 			o[0] = __builtin_amdgcn_perm(n[1], n[0], 0x06040200);
 			o[1] = __builtin_amdgcn_perm(n[3], n[2], 0x06040200);
 		}
@@ -1128,7 +1148,7 @@ template <int DEPTH, bool ONEY, bool ONEC, bool WIDE>
 constexpr int rw_waves_per_simd()
 {
 #ifdef VFGS_ONE10_WAVES      // developer A/B: the 10-bit all-one-pattern kernels at another occupancy
-	if (DEPTH == 10 && ONEY && ONEC && !WIDE) return VFGS_ONE10_WAVES;
+	if (DEPTH > 8 && ONEY && ONEC && !WIDE) return VFGS_ONE10_WAVES;
 #endif
 	return (DEPTH == 8 && ONEY && ONEC && !WIDE && VFGS_WG_PER_CU == 4) ? (kPk16 ? VFGS_PK_WAVES : 5) : (kWavesPerWG * VFGS_WG_PER_CU + 3) / 4;
 }
@@ -1139,7 +1159,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 {
 	constexpr ImageLayout L = image_layout(CSUBX, CSUBY, ONEY, ONEC, DEPTH == 8);
 	// (unused LDS behind the tables holds a kernel at no more than its class's workgroups per CU: vfgs_layout.h lds_allocation)
-	__shared__ __attribute__((aligned(16))) uint8_t lds[lds_allocation(DEPTH == 10, ONEY, ONEC, WIDE, L.lds_bytes + kParamBytes)];
+	__shared__ __attribute__((aligned(16))) uint8_t lds[lds_allocation(DEPTH > 8, ONEY, ONEC, WIDE, L.lds_bytes + kParamBytes)];
 
 	const int lane = threadIdx.x & 63;
 	// wave-uniform by construction; telling the compiler keeps the decoding, row offsets and buffer descriptors in SGPRs
@@ -1264,7 +1284,7 @@ static hipError_t launch_form(const KernelArgs& a, const FrameTable& ft, bool on
 		}
 		return (oney || onec) ? hipErrorInvalidValue : launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, false, true, false>(a, ft, grid, stream);
 	}
-	if constexpr (DEPTH == 10)     // (the host asks for persistence at 10 bit only)
+	if constexpr (DEPTH > 8)     // (the host asks for persistence at 10 and 12 bit only)
 	{
 		if (persist)
 		{
@@ -1280,13 +1300,13 @@ static hipError_t launch_form(const KernelArgs& a, const FrameTable& ft, bool on
 	return launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, false, false, false>(a, ft, grid, stream);
 }
 
-// out8: the destination holds 8-bit samples of a 10-bit path; oney / onec: the image holds the one-pattern form for luma /
+// out8: the destination holds 8-bit samples of a 10- or 12-bit path; oney / onec: the image holds the one-pattern form for luma /
 // chroma (vfgs_layout.h); wide: rows of more than kTileBlocks blocks (launch_form: which forms exist); persist: a.persist_wgs luma workgroups
-// share the launch's luma tasks (10 bit, general-form luma, not wide), grid = persist_wgs + all chroma tasks; else grid =
+// share the launch's luma tasks (10 and 12 bit, general-form luma, not wide), grid = persist_wgs + all chroma tasks; else grid =
 // workgroups per frame
 //
-// The product compiles this file TWICE (versatilefilmgrain_amd/build.py: -DVFGS_KERNEL_DEPTH=10 and =8), side by side: one code object per
-// sample depth, 56 + 32 kernels.  That halves the build (110 -> 60 s) and keeps the other depth's kernels off the device; it does NOT buy the
+// The product compiles this file THREE times (versatilefilmgrain_amd/build.py: -DVFGS_KERNEL_DEPTH=10, =8 and =12), side by side: one code object per
+// sample depth; the 12-bit one holds the 10-bit one's row-walk kernels (same forms, same residency) and no mix kernels.  That halves the build (110 -> 60 s) and keeps the other depth's kernels off the device; it does NOT buy the
 // start-up time round 5 hoped for: a code object's first launch costs 1.3 ms (profiles/r06_startup_probe_two_code_objects.jsonl), so the 15 ms
 // of a process's first grain launch are the allocations and first transfers around it, not the 88 kernels.  Without the macro (the assembly
 // listings) everything is one translation unit.
@@ -1295,12 +1315,13 @@ static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int cs
 {
 	if (a.mix_kernel)
 	{
+		// (no mix kernels at 12 bit: launch_depth<12> instantiates none, the host refuses such a call before it gets here)
 		if (!oney || !onec || persist) return hipErrorInvalidValue;
 #define VFGS_CASE(X, Y)                                                                                  \
 	if (csubx == X && csuby == Y)                                                                        \
 	{                                                                                                    \
 		if constexpr (D == 10) { if (out8) return launch_mix<D, X, Y, true>(a, ft, wide, grid, stream); } \
-		return launch_mix<D, X, Y, false>(a, ft, wide, grid, stream);                                     \
+		if constexpr (D != 12) return launch_mix<D, X, Y, false>(a, ft, wide, grid, stream);              \
 	}
 		VFGS_CASE(2, 2) VFGS_CASE(2, 1) VFGS_CASE(1, 1) VFGS_CASE(1, 2)
 #undef VFGS_CASE
@@ -1309,7 +1330,7 @@ static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int cs
 #define VFGS_CASE(X, Y)                                                                                                     \
 	if (csubx == X && csuby == Y)                                                                                           \
 	{                                                                                                                       \
-		if constexpr (D == 10) { if (out8) return launch_form<D, X, Y, true>(a, ft, oney, onec, wide, persist, grid, stream); } \
+		if constexpr (D > 8) { if (out8) return launch_form<D, X, Y, true>(a, ft, oney, onec, wide, persist, grid, stream); }   \
 		return launch_form<D, X, Y, false>(a, ft, oney, onec, wide, persist, grid, stream);                                     \
 	}
 	VFGS_CASE(2, 2) VFGS_CASE(2, 1) VFGS_CASE(1, 1) VFGS_CASE(1, 2)
@@ -1326,16 +1347,26 @@ hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable& ft, int csubx,
 hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream);
 #endif
 
+#if !defined(VFGS_KERNEL_DEPTH) || VFGS_KERNEL_DEPTH == 12
+hipError_t launch_grain_d12(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
+{
+	return launch_depth<12>(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
+}
+#else
+hipError_t launch_grain_d12(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream);
+#endif
+
 #if !defined(VFGS_KERNEL_DEPTH) || VFGS_KERNEL_DEPTH == 10
 hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
 {
-	if ((out8 && depth != 10) || wide != (a.nblk > kTileBlocks)) return hipErrorInvalidValue;
+	if ((out8 && depth != 10 && depth != 12) || wide != (a.nblk > kTileBlocks)) return hipErrorInvalidValue;
 	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return hipErrorInvalidValue;
 	if ((a.listed != 0) != (list != nullptr) || (list && a.nframes > kListFrames)) return hipErrorInvalidValue;
 	static const FrameTable no_list{};
 	const FrameTable& ft = list ? *list : no_list;
 	if (depth == 10) return launch_depth<10>(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
 	if (depth == 8) return launch_grain_d8(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
+	if (depth == 12) return launch_grain_d12(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
 	return hipErrorInvalidValue;
 }
 

@@ -92,6 +92,8 @@ constexpr int kParamBytes = 2 * kParamTableBytes;
 // workgroups per CU than would fit (VFGS_ONE10_WG_PER_CU / VFGS_ONE8_WG_PER_CU above): a size with which exactly that many are resident.
 // The kernels with one-pattern luma at 10 bit (rows walked in parts included: 92-95 registers, five would be resident -- 16384-wide AFGS1 +2.5 % at two
 // frames per launch, +1 % at four: profiles/r06_ab18) need 15 KB and allocate 40; the kernels with a general-form plane are at four by their 40 KB image.
+// (depth10: the 16-bit containers, 10 AND 12 bit -- a 12-bit kernel moves the same bytes through the same LDS image as its 10-bit twin and gets
+// every decision of it: this allocation, the ring depths VFGS_RING_ONE10 / VFGS_RING_NARROW10 above, persistence)
 constexpr int kLdsPerCU = 163840;
 constexpr int lds_allocation(const bool depth10, const bool one_y, const bool one_c, const bool wide, const int need)
 {
@@ -152,7 +154,8 @@ constexpr int mix_lds_allocation(const int need)
 // two samples per v_and_or_b32.  Entry:
 //   bits 31:24 byte selector for v_perm_b32: slot 0..7, or 0x0c (constant zero) for slot 8
 //              (the reference's never-written 9th slot, vfgs_hw.c:49); unused in the one-pattern form
-//   bits 23:0  signed scale factor (+-sLUT), pre-shifted: scale << (16 - scale_shift)
+//   bits 23:0  signed scale factor (+-sLUT), pre-shifted: scale << (16 - scale_shift); the stored shift is 8..13 at 8 bit, 6..11 at 10 bit,
+//              4..9 at 12 bit (shift + 6 - bs), so an entry reaches 255 << 12 < 2^23 (ranges: vfgs_kernel.hip grain_unit "scale, add, clip")
 struct ImageLayout {
 	int lut_bytes;              // one component: +scale table, -scale table
 	int y_rs, c_rs;             // bank row strides, bytes
@@ -242,7 +245,7 @@ struct KernelArgs {
 	int lfronts;              // log2 of the frames of a batch that are swept at the same time (their workgroups are dealt out in turn)
 	int persist_wgs;          // PERSIST kernels: P luma workgroups share the launch's nframes x pd[0].wgs luma tasks (task t -> workgroup t % P) ...
 	int persist_step_f, persist_step_r;   // ... and P = persist_step_f * pd[0].wgs + persist_step_r: what a workgroup advances by
-	int pk_shift;             // 8-bit one-pattern forms (packed 16-bit form, above): the scale shift of vfgs_hw.c:263, 8..13
+	int pk_shift;             // 8-bit one-pattern forms (packed 16-bit form, above): the scale shift of vfgs_hw.c:263, 8..13 (other depths: unused)
 	uint32_t lo2[2], hi2[2];  // clip bounds in sample units (I_min<<bs ...) in both halves of a dword, per plane type (vfgs_hw.c:264-267)
 	// Luma / chroma mix of the chroma look-up index (vfgs_hip_set_chroma_mix; all zero = the kernels and the launch of always)
 	int mix_kernel;           // 1: grain_mix_kernel serves the launch (all-one-pattern images only)

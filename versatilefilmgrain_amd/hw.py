@@ -132,6 +132,7 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_clear_chroma_mix.argtypes = []
     lib.vfgs_hip_clear_chroma_mix.restype = None
     lib.vfgs_hip_get_chroma_mix.argtypes = [i, C.POINTER(i)]
+    lib.vfgs_hip_supports_depth.argtypes = [i]
     # a library built by a developer tool with tuning / ablation knobs may compute something else by design: only on request
     if lib.vfgs_hip_dev_build() and not os.environ.get("VFGS_ALLOW_DEV_BUILD"):
         raise VfgsHipError(f"{path} is a developer build (tuning / ablation knobs); set VFGS_ALLOW_DEV_BUILD=1 to load it anyway")
@@ -167,7 +168,7 @@ EXPORTS = [
     "vfgs_hip_dev_build", "vfgs_hip_init_devices", "vfgs_hip_overlap_begin", "vfgs_hip_overlap_end", "vfgs_hip_get_stream_stats", "vfgs_hip_line_lookahead", "vfgs_hip_declare_frame",
     "vfgs_hip_get_stripe_stream_stats", "vfgs_hip_lfsr_segments",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
-    "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix",
+    "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
 ]
 
 
@@ -197,6 +198,7 @@ class VfgsHip:
     def set_seed(self, s):                  self.lib.vfgs_set_seed(s & 0xFFFFFFFF)
     def set_scale_shift(self, s):           self.lib.vfgs_set_scale_shift(s)
     def set_depth(self, d):                 self.lib.vfgs_set_depth(d)
+    def supports_depth(self, d):            return bool(self.lib.vfgs_hip_supports_depth(d))     # (vfgs_set_depth aborts on any other)
     def set_legal_range(self, l):           self.lib.vfgs_set_legal_range(l)
     def set_chroma_subsampling(self, x, y): self.lib.vfgs_set_chroma_subsampling(x, y)
 
