@@ -207,6 +207,45 @@ int vfgs_hip_add_grain_frame_list_copy8_dev(const vfgs_hip_frame_ptrs* src, cons
                                             unsigned width, unsigned height, unsigned stride, unsigned cstride,
                                             unsigned dst_stride, unsigned dst_cstride, void* stream);
 
+/* The list calls with A SEED PER PICTURE.  The calls above treat their frames as one seed sequence (frame f + 1 continues frame f's
+ * registers); AFGS1 carries a grain_seed per picture (vfgs_init_afgs1 calls vfgs_set_seed for each, vfgs_fw.c:672; vfgs_hip_afgs1_seed
+ * in vfgs_hip_fw.h), and a player that reseeds an SEI model per picture is in the same position.  seeds: host memory, `nframes` values,
+ * read during the call only, each exactly what the caller would pass to vfgs_set_seed.  Samples and seed registers afterwards are those of
+ *     for f in list order: vfgs_set_seed(seeds[f]); vfgs_hip_add_grain_frame_dev(frame f)
+ * (_part: vfgs_hip_add_grain_frame_part_dev in that loop; _copy / _copy8: their single-frame forms) in ONE launch per 32 frames.  After
+ * the call the library is where vfgs_set_seed(seeds[nframes - 1]) and one whole frame leave it: a later call without seeds continues
+ * that picture's stream, as the reference would.  If a later launch of a list of more than 32 frames fails with a HIP error, the
+ * registers are those behind the last launch that was queued.
+ * Everything the list calls above refuse is refused here, with the same codes, before anything changes -- in particular a refused call
+ * does NOT reseed -- plus seeds == NULL with nframes > 0 (error 39).  An empty list is no call at all.  An active chroma mix is
+ * honoured; inside an overlap region the calls alternate over the two internal streams like every other device-pointer call.
+ * Cost: the library builds one short run of the LFSR stream per frame on the host (vfgs_hip_seed_segments below; about a microsecond per
+ * 1080p frame) and uploads them in the caller's stream in front of the launch -- 34 KB for 1080p x 32, 130 KB for 4320p x 8.  That copy
+ * in front of the kernel costs 11 .. 20 us per launch: 1080p x 32 / 2160p x 16 / 4320p x 8 run at 2.72 / 9.30 / 36.1 us per frame against
+ * 2.37 / 8.06 / 33.7 without seeds and 19.3 / 22.6 / 62.5 with vfgs_set_seed + one frame per launch (profiles/per_picture_seeds.json). */
+int vfgs_hip_add_grain_frame_list_seeded_dev(const vfgs_hip_frame_ptrs* frames, const uint32_t* seeds, unsigned nframes, unsigned width,
+                                             unsigned height, unsigned stride, unsigned cstride, void* stream);
+int vfgs_hip_add_grain_frame_list_seeded_part_dev(const vfgs_hip_frame_ptrs* frames, const uint32_t* seeds, unsigned nframes,
+                                                  unsigned width, unsigned frame_height, unsigned part_y, unsigned part_height,
+                                                  unsigned stride, unsigned cstride, void* stream);
+int vfgs_hip_add_grain_frame_list_seeded_copy_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
+                                                  unsigned nframes, unsigned width, unsigned height, unsigned stride, unsigned cstride,
+                                                  void* stream);
+int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
+                                                   unsigned nframes, unsigned width, unsigned height, unsigned stride, unsigned cstride,
+                                                   unsigned dst_stride, unsigned dst_cstride, void* stream);
+/* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
+ * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).
+ * `out` holds nseg * seg_words 32-bit words.  first_bit is reached by one jump (a 32 x 32 bit matrix, log2(first_bit) squarings),
+ * never by stepping.  For a launch over lines [part_y, part_y + part_height) of pictures `width` wide the library uses, with
+ * nblk = ceil(width / 16), b = part_y / 16 and nbr = the block rows the part touches: first_bit = max(b - 1, 0) * nblk,
+ * seg_words = ceil((32 + nblk + nbr * nblk + 64) / 32) + 1.  0, or error 19 (a null pointer, nseg or seg_words 0). */
+int vfgs_hip_seed_segments(const uint32_t* seeds, unsigned nseg, uint64_t first_bit, unsigned seg_words, uint32_t* out);
+/* out[4] = { seeded images built and uploaded (one per launch), 32-bit words of the most recent one, calls that waited on the host
+ * (longer than 20 us) for a slot of the images' ring -- a slot packs the images of consecutive calls, 256 KiB by default, and is
+ * overwritten only after every kernel that read it --, 1 if the most recent launch read a seeded image }. */
+void vfgs_hip_get_seeded_stream_stats(uint64_t out[4]);
+
 /* {rnd, rnd_up, line_rnd, line_rnd_up} as the reference would hold them (vfgs_hw.c:52-55). */
 void vfgs_hip_get_seed_state(uint32_t out[4]);
 

@@ -93,6 +93,11 @@ void vfgs_init_afgs1(fgs_afgs1* cfg);
  * With the switch off vfgs_init_afgs1 clears the mix; vfgs_init_sei always clears it. */
 void vfgs_hip_afgs1_chroma_mix(int enable);
 
+/* The value vfgs_init_afgs1 passes to vfgs_set_seed for this picture: grain_seed | grain_seed << 16 (vfgs_fw.c:672).  A caller that
+ * collects consecutive pictures sharing one model programs the model once and hands their seeds to
+ * vfgs_hip_add_grain_frame_list_seeded_dev (vfgs_hip.h) -- this is the seed of each.  Host only, no GPU needed. */
+unsigned int vfgs_hip_afgs1_seed(const fgs_afgs1* cfg);
+
 /* One grain pattern to be generated on the device into pattern slot `index`. */
 typedef struct vfgs_hip_pattern_job {
 	int32_t kind;       /* 0: frequency filtered (vfgs_fw.c:362-408), 1: auto-regressive (vfgs_fw.c:410-502) */

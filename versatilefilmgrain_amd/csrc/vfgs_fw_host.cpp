@@ -241,13 +241,18 @@ void vfgs_hip_afgs1_chroma_mix(int enable)
 	g_afgs1_mix.store(enable != 0);
 }
 
+unsigned int vfgs_hip_afgs1_seed(const fgs_afgs1* cfg)
+{
+	return cfg->grain_seed | ((uint32_t)cfg->grain_seed << 16);   // vfgs_fw.c:672
+}
+
 void vfgs_init_afgs1(fgs_afgs1* cfg)
 {
 	unsigned char lut[256];
 	vfgs_hip_pattern_job jobs[3];
 	const int lag = cfg->ar_coeff_lag;
 
-	vfgs_set_seed(cfg->grain_seed | ((uint32_t)cfg->grain_seed << 16));   // vfgs_fw.c:672
+	vfgs_set_seed(vfgs_hip_afgs1_seed(cfg));
 
 	scaling_lut(lut, cfg->point_y_values, cfg->point_y_scaling, cfg->num_y_points);
 	vfgs_set_scale_lut(0, lut);

@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -746,6 +747,92 @@ struct DevRing {
 	}
 };
 
+// The stream of a LIST OF FRAMES WITH A SEED EACH (vfgs_hip_add_grain_frame_list_seeded_*: AFGS1 carries a grain_seed per picture,
+// vfgs_fw.c:672).  The same image as StripeStream's -- nseg segments of seg_words words back to back, seg_words x 32 as the kernel's
+// frame_bit_step -- with another rule for the head of a segment: segment f is the stream of the register seeds[f] << 1
+// (vfgs_hw.c:339-344) from bit first_bit on.  The seeds arrive with the call, so nothing can be built ahead: every call builds its
+// image in pinned memory (a jump to first_bit, 32 head words by a 32-step jump each, the rest by the word recurrence) and uploads it in
+// its own stream in front of its launch.  The images of consecutive calls are packed into one slot of a ring of this stream's own
+// (StripeStream keeps its slots, and the images built ahead in them) until the slot is full: a slot is only LEFT, with the event per
+// user stream that costs (SlotGuard), once per several calls, and only overwritten after everything that read it.
+class SeededStream {
+public:
+	struct Image { const uint32_t* dev; uint32_t words; };
+
+	// out[f * seg_words + k] = the register after first_bit + 32 k steps from seeds[f] << 1 (host only)
+	static void fill(const uint32_t* seeds, unsigned nseg, uint64_t first_bit, unsigned seg_words, LfsrJump& jump, uint32_t* out)
+	{
+		static const LfsrJump word = [] { LfsrJump j; j.build(32); return j; }();     // one word on: 32 steps
+		if (first_bit) jump.build(first_bit);          // (one matrix per call, log2(first_bit) squarings; kept while first_bit stays)
+		const unsigned nhead = std::min(32u, seg_words);
+		for (unsigned f = 0; f < nseg; f++)
+		{
+			uint32_t* w = out + (size_t)f * seg_words;
+			uint32_t reg = seeds[f] << 1;              // vfgs_hw.c:343
+			if (first_bit) reg = jump(reg);
+			for (unsigned i = 0; i < nhead; i++) { w[i] = reg; reg = word(reg); }
+			lfsr_extend(w, seg_words);
+		}
+	}
+
+	hipError_t upload(const uint32_t* seeds, unsigned nseg, uint64_t first_bit, unsigned seg_words, hipStream_t stream, Image* out)
+	{
+		const size_t bytes = (size_t)nseg * seg_words * 4;
+		hipError_t e;
+		const bool fresh = ring_.cur < 0 || off_ + bytes > limit_;
+		if (fresh)
+		{
+			// the slot behind the current one: its readers have normally long finished; a caller that queues calls faster than the GPU
+			// serves them waits here
+			SlotGuard& g = ring_.guard[(ring_.cur + 1) % DevRing::N];
+			if (g.nleft)
+			{
+				const auto t0 = std::chrono::steady_clock::now();
+				if ((e = g.wait_free()) != hipSuccess) return e;
+				if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kWaitUs)) stats_[2]++;
+			}
+			void* d = nullptr;
+			uint8_t* h = nullptr;
+			limit_ = std::max(bytes, slot_bytes());
+			if ((e = ring_.next(limit_, &d, &h)) != hipSuccess) return e;
+			off_ = 0;
+		}
+		uint32_t* host = (uint32_t*)(ring_.host[ring_.cur] + off_);
+		uint32_t* dev = (uint32_t*)((uint8_t*)ring_.buf[ring_.cur] + off_);
+		fill(seeds, nseg, first_bit, seg_words, jump_, host);
+		if ((e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+		// (the launch that reads this image follows its upload in the same stream; the guard only has to know the streams)
+		if ((e = fresh ? ring_.uploaded(stream) : ring_.use(stream)) != hipSuccess) return e;
+		off_ += (bytes + 255) & ~(size_t)255;
+		stats_[0]++;
+		stats_[1] = (uint64_t)nseg * seg_words;
+		out->dev = dev;
+		out->words = nseg * seg_words;
+		return hipSuccess;
+	}
+
+	// {images built, words of the most recent one, calls that waited on the host for a slot}
+	void stats(uint64_t out[3]) const { out[0] = stats_[0]; out[1] = stats_[1]; out[2] = stats_[2]; }
+
+	void release() { ring_.release(); off_ = limit_ = 0; }
+
+private:
+	static constexpr int kWaitUs = 20;      // a synchronisation that returns faster than this found its events complete
+	// bytes of a slot (a larger image gets a slot of its own size): 256 KiB = 7 calls of 1080p x 32, 2 of 4320p x 8.  The environment
+	// variable VFGS_HIP_SEEDED_SLOT_KB sets another size, 0 = every image in a slot of its own (the tests: a ring that turns over
+	// quickly); read when a slot is opened, not per call
+	static size_t slot_bytes()
+	{
+		const char* e = getenv("VFGS_HIP_SEEDED_SLOT_KB");
+		const long kb = e ? atol(e) : 256;
+		return (size_t)std::min(65536L, std::max(0L, kb)) << 10;
+	}
+	DevRing ring_;
+	size_t off_ = 0, limit_ = 0;            // first free byte of the current slot; the bytes it takes
+	LfsrJump jump_;
+	uint64_t stats_[3] = {0, 0, 0};
+};
+
 // ------------------------------------------------------------------------------------
 // the singleton
 
@@ -763,6 +850,8 @@ struct State {
 	StreamCache lfsr;
 	StripeStream stripes;               // the stream of batches of stripes (jump-ahead; run_device)
 	bool stripe_stream_last = false;    // the last launch read its LFSR windows from `stripes`
+	SeededStream seeded;                // the streams of a list of frames with a seed each (run_device)
+	bool seeded_stream_last = false;    // the last launch read its LFSR windows from `seeded`
 	uint64_t rnd = 0, rnd_up = 0, line_rnd = 0, line_rnd_up = 0;
 
 	// device
@@ -1334,6 +1423,14 @@ int check_geometry(const State& s, const void* dY, const void* dU, const void* d
 	return 0;
 }
 
+// vfgs_set_seed (vfgs_hw.c:339-344): seed << 1 into all four registers
+void load_seed(State& s, uint32_t seed)
+{
+	s.lfsr.reseed(seed << 1);   // vfgs_hw.c:343
+	s.seed_epoch++;             // (the replicas of vfgs_hip_init_devices resynchronise; StripeStream's chain dies with the cache's epoch)
+	s.rnd = s.rnd_up = s.line_rnd = s.line_rnd_up = 0;
+}
+
 // Core: launch the kernel over `nframes` frames, lines [part_y, part_y+part_h) of each.
 struct DstGeom {          // destination geometry when it differs from the source's (8-bit output of a 10- or 12-bit path)
 	bool out8 = false;
@@ -1344,7 +1441,8 @@ struct DstGeom {          // destination geometry when it differs from the sourc
 int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV, unsigned width,
                unsigned frame_y, unsigned frame_h, unsigned part_y, unsigned part_h, unsigned stride, unsigned cstride,
                unsigned nframes, uint64_t ypitch, uint64_t cpitch, hipStream_t stream, DstGeom dg = DstGeom(),
-               const vfgs::FrameTable* list = nullptr)     // list: the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
+               const vfgs::FrameTable* list = nullptr,     // list: the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
+               const uint32_t* seeds = nullptr)            // seeds: frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
 {
 	State& s = S();
 	if (list && nframes > (unsigned)vfgs::kListFrames) return fail(19, "internal: a listed launch holds at most %d frames", vfgs::kListFrames);
@@ -1362,6 +1460,8 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		if ((((uintptr_t)dY | (uintptr_t)dU | (uintptr_t)dV) & 15) || dg.stride % 16 || dg.cstride % 16 || (dg.ypitch | dg.cpitch) % 16)
 			return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
 	}
+	if (seeds && (frame_y != 0 || !list)) return fail(19, "internal: seeds belong to lists of frames that begin at line 0");
+	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) return 0;
 	if (int e = check_luts(s)) return e;     // before any state moves: a refused call leaves the seed registers alone
 
@@ -1441,8 +1541,22 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	// all four registers move by the same amount per frame -- a frame of nbr block rows rotates nbr - 1 times (not at line 0) and
 	// every rotation moves line_rnd, and line_rnd_up behind it, by one row of blocks: G = f (nbr - 1) + r, SURVEY 8a -- so the
 	// frames behind them are one addition each register, whatever the batch size
+	//
+	// With a seed per frame every frame begins at bit 0 of a stream of its own: block row b reads its registers at b x nblk and, for the row
+	// above it, (b - 1) x nblk (the machine run from zeroed registers), the same positions in every frame.  The registers themselves move
+	// behind the launch (seeded_done): a call that fails before it is queued leaves them where they were.
 	uint64_t first_cur = 0, first_up = 0, second_cur = 0, lo = ~0ull, hi = 0;
-	for (unsigned f = 0; f < nframes && f < 2; f++)
+	if (seeds)
+	{
+		const uint64_t b = part_y >> 4;
+		first_cur = b * nblk;
+		first_up = b ? (b - 1) * nblk : 0;
+	}
+	auto seeded_done = [&] {     // the state vfgs_set_seed(seeds[nframes - 1]) + one whole frame leaves
+		load_seed(s, seeds[nframes - 1]);
+		advance_seeds(s, 0, frame_h, nblk, 0);
+	};
+	for (unsigned f = 0; f < nframes && f < 2 && !seeds; f++)
 	{
 		StripePlan p = advance_seeds(s, frame_y, frame_h, nblk, part_y);
 		if (f == 0) { first_cur = p.cur0; first_up = p.up0; }
@@ -1451,7 +1565,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		hi = std::max(hi, p.cur0 + (uint64_t)nbr_stripe * nblk);
 		hi = std::max(hi, p.up0 + nblk);
 	}
-	if (nframes > 2)
+	if (nframes > 2 && !seeds)
 	{
 		if (frame_y != 0) return fail(10, "internal: a batch of stripes that do not begin at line 0");
 		const uint64_t step = second_cur - first_cur, more = (uint64_t)(nframes - 2) * step;
@@ -1470,10 +1584,23 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	const uint64_t seg_bits = 32 + (uint64_t)nblk + (uint64_t)nbr_stripe * nblk + 64;
 	const unsigned seg_words = (unsigned)((seg_bits + 31) / 32) + 1;
 	static const bool jump_on = [] { const char* e = getenv("VFGS_HIP_STRIPE_JUMP"); return !(e && e[0] == '0'); }();
-	const bool stripes = jump_on && nframes >= 2 && first_cur >= (uint64_t)nblk + 32 && first_up + nblk + 32 >= first_cur &&
+	const bool stripes = !seeds && jump_on && nframes >= 2 && first_cur >= (uint64_t)nblk + 32 && first_up + nblk + 32 >= first_cur &&
 	                     (uint64_t)seg_words * 32 * 4 <= frame_step * 3;      // (the segments are at most three quarters of what lies between them)
 	s.stripe_stream_last = stripes;
-	if (stripes)
+	s.seeded_stream_last = seeds != nullptr;
+	if (seeds)
+	{
+		// segment f = the stream of seeds[f] << 1 from the row above the part's first block row on (bit 0 for a part that begins at line 0)
+		const uint64_t seg0 = first_up;
+		SeededStream::Image img{};
+		HIP_TRY(s.seeded.upload(seeds, nframes, seg0, seg_words, stream, &img));
+		a.stream = img.dev;
+		a.stream_bytes = img.words * 4;
+		a.cur_bit0 = (uint32_t)(first_cur - seg0);
+		a.up_bit0 = 0;
+		a.frame_bit_step = seg_words * 32;
+	}
+	else if (stripes)
 	{
 		const uint64_t seg0 = first_cur - nblk - 32;
 		StripeStream::Image img{};
@@ -1498,7 +1625,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	// one workgroup per (frame, plane, block row, part of it), numbered in memory order
 	const long per_frame = (long)a.pd[0].wgs + 2L * a.pd[1].wgs;
 	if (per_frame > 0x3fffffffL || nframes > 65535) return fail(14, "launch too large");
-	if (per_frame == 0) return 0;
+	if (per_frame == 0) { if (seeds) seeded_done(); return 0; }
 	// General-form luma of small pictures: a workgroup stages 36 KB of tables for 15-30 KB of samples.  Where a launch holds several
 	// rounds of luma workgroups, P persistent ones share the luma tasks instead (task t -> workgroup t % P, so they sweep the frames
 	// in memory order together); chroma keeps one workgroup per task behind them in the grid.
@@ -1561,6 +1688,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		}
 	}
 	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist, (int)grid, stream));
+	if (seeds) seeded_done();
 	// the stream of the batches behind this one, while the GPU works on this one.  (Failing to work ahead is not a failure of THIS call, which is
 	// queued and whose registers have moved: the next call then builds its image in its own stream.)
 	if (stripes && s.stripes.prepare_next(s.lfsr) != hipSuccess) (void)hipGetLastError();
@@ -2352,6 +2480,7 @@ void release_state_impl(State& s)
 	s.tables_ring.release();
 	s.lfsr.release();
 	s.stripes.release();
+	s.seeded.release();
 	for (int i = 0; i < 3; i++) { if (s.stage[i]) (void)hipFree(s.stage[i]); s.stage[i] = nullptr; s.stage_cap[i] = 0; }
 	for (int i = 0; i < 3; i++) { if (s.bounce[i]) (void)hipHostFree(s.bounce[i]); s.bounce[i] = nullptr; s.bounce_cap[i] = 0; }
 	s.pipe.release();
@@ -2445,10 +2574,7 @@ void vfgs_set_seed(unsigned int seed)
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	State& s = S();
-	s.lfsr.reseed(seed << 1);   // vfgs_hw.c:343
-	s.seed_epoch++;
-	s.rnd = s.rnd_up = s.line_rnd = s.line_rnd_up = 0;
+	load_seed(S(), seed);
 }
 
 void vfgs_set_scale_shift(int shift)
@@ -2756,12 +2882,14 @@ int vfgs_hip_add_grain_frames_part_dev(void* dY, void* dU, void* dV, unsigned wi
 // Frames anywhere in device memory (vfgs_hip.h): validated as a whole before anything moves, then launched in chunks of
 // kListFrames frames whose plane pointers travel in the kernel arguments.
 static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, unsigned nframes, unsigned width, unsigned height,
-                          unsigned stride, unsigned cstride, hipStream_t stream, DstGeom dg, bool whole = true, unsigned part_y = 0, unsigned part_h = 0)
+                          unsigned stride, unsigned cstride, hipStream_t stream, DstGeom dg, bool whole = true, unsigned part_y = 0, unsigned part_h = 0,
+                          bool seeded = false, const uint32_t* seeds = nullptr)     // seeded: frame f is the frame behind vfgs_set_seed(seeds[f])
 {
 	if (whole) { part_y = 0; part_h = height; }
 	State& s = S();
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
+	if (seeded && !seeds) return fail(39, "seeded frame list: null seeds for %u frames", nframes);
 	if (!src || !dst) return fail(18, "frame list: null list");
 	for (unsigned f = 0; f < nframes; f++)
 	{
@@ -2819,7 +2947,7 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			ft.dst[0][k] = (uint8_t*)b.Y; ft.dst[1][k] = (uint8_t*)b.U; ft.dst[2][k] = (uint8_t*)b.V;
 		}
 		if (int e = run_device(src[f0].Y, src[f0].U, src[f0].V, dst[f0].Y, dst[f0].U, dst[f0].V, width, 0, height, part_y, part_h, stride, cstride,
-		                       n, 0, 0, stream, dg, &ft))
+		                       n, 0, 0, stream, dg, &ft, seeded ? seeds + f0 : nullptr))
 			return e;
 	}
 	return 0;
@@ -2861,6 +2989,47 @@ int vfgs_hip_add_grain_frame_list_copy8_dev(const vfgs_hip_frame_ptrs* src, cons
 	dg.out8 = true;
 	dg.stride = dst_stride; dg.cstride = dst_cstride;
 	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), dg);
+}
+
+int vfgs_hip_add_grain_frame_list_seeded_dev(const vfgs_hip_frame_ptrs* frames, const uint32_t* seeds, unsigned nframes, unsigned width,
+                                             unsigned height, unsigned stride, unsigned cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	return run_frame_list(frames, frames, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom(), true, 0, 0, true, seeds);
+}
+
+int vfgs_hip_add_grain_frame_list_seeded_part_dev(const vfgs_hip_frame_ptrs* frames, const uint32_t* seeds, unsigned nframes, unsigned width,
+                                                  unsigned frame_height, unsigned part_y, unsigned part_height, unsigned stride,
+                                                  unsigned cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
+	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
+	return run_frame_list(frames, frames, nframes, width, frame_height, stride, cstride, pick_stream(stream), DstGeom(), false, part_y, part_height,
+	                      true, seeds);
+}
+
+int vfgs_hip_add_grain_frame_list_seeded_copy_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
+                                                  unsigned nframes, unsigned width, unsigned height, unsigned stride, unsigned cstride,
+                                                  void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom(), true, 0, 0, true, seeds);
+}
+
+int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
+                                                   unsigned nframes, unsigned width, unsigned height, unsigned stride, unsigned cstride,
+                                                   unsigned dst_stride, unsigned dst_cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	DstGeom dg;
+	dg.out8 = true;
+	dg.stride = dst_stride; dg.cstride = dst_cstride;
+	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), dg, true, 0, 0, true, seeds);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,
@@ -2997,6 +3166,22 @@ int vfgs_hip_lfsr_segments(unsigned int reg, uint64_t first_bit, uint64_t step_b
 	lfsr.reseed(reg);
 	gen.generate(lfsr, first_bit, step_bits, nseg, seg_words, out);
 	return 0;
+}
+
+int vfgs_hip_seed_segments(const uint32_t* seeds, unsigned nseg, uint64_t first_bit, unsigned seg_words, uint32_t* out)
+{
+	// (host only: a jump table of its own, nothing of the library's state is touched)
+	if (!seeds || !out || !nseg || !seg_words) return fail(19, "vfgs_hip_seed_segments: nothing to fill");
+	LfsrJump jump;
+	SeededStream::fill(seeds, nseg, first_bit, seg_words, jump, out);
+	return 0;
+}
+
+void vfgs_hip_get_seeded_stream_stats(uint64_t out[4])
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().seeded.stats(out);
+	out[3] = S().seeded_stream_last ? 1 : 0;
 }
 
 void vfgs_hip_get_stripe_stream_stats(uint64_t out[4])

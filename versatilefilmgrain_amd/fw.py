@@ -14,7 +14,7 @@ SEI_MAX_MODEL_VALUES = 6   # vfgs_fw.h:49
 
 EXPORTS = ["vfgs_init_sei", "vfgs_init_afgs1", "vfgs_hip_generate_patterns", "vfgs_hip_get_pattern",
            "vfgs_hip_cfg_defaults", "vfgs_hip_cfg_read", "vfgs_hip_cfg_check", "vfgs_hip_cfg_adjust_chroma",
-           "vfgs_hip_cfg_apply_gain", "vfgs_hip_cfg_program", "vfgs_hip_afgs1_chroma_mix"]
+           "vfgs_hip_cfg_apply_gain", "vfgs_hip_cfg_program", "vfgs_hip_afgs1_chroma_mix", "vfgs_hip_afgs1_seed"]
 
 
 class FgsSei(C.Structure):   # vfgs_fw.h:51-60
@@ -121,6 +121,8 @@ def _lib():
         lib.vfgs_hip_cfg_program.restype = None
         lib.vfgs_hip_afgs1_chroma_mix.argtypes = [C.c_int]
         lib.vfgs_hip_afgs1_chroma_mix.restype = None
+        lib.vfgs_hip_afgs1_seed.argtypes = [C.POINTER(FgsAfgs1)]
+        lib.vfgs_hip_afgs1_seed.restype = C.c_uint
         lib._fw_typed = True
     return lib
 
@@ -144,6 +146,11 @@ def init_afgs1(cfg: FgsAfgs1) -> None:
 def afgs1_chroma_mix(enable: bool) -> None:
     """Process-wide: init_afgs1 also programs the luma / chroma mix of cb_mult, cb_luma_mult, cb_offset (include/vfgs_hip_fw.h)."""
     _lib().vfgs_hip_afgs1_chroma_mix(1 if enable else 0)
+
+
+def afgs1_seed(cfg: FgsAfgs1) -> int:
+    """What init_afgs1 passes to vfgs_set_seed for this picture (vfgs_fw.c:672): the seed of hw.VfgsHip.add_grain_frame_list_seeded_dev."""
+    return _lib().vfgs_hip_afgs1_seed(C.byref(cfg))
 
 
 def init(cfg) -> None:

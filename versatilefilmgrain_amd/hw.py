@@ -111,6 +111,14 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_add_grain_frame_list_part_dev.argtypes = [fp, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_copy_dev.argtypes = [fp, fp, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_copy8_dev.argtypes = [fp, fp, u, u, u, u, u, u, u, vp]
+    sp = C.POINTER(C.c_uint32)
+    lib.vfgs_hip_add_grain_frame_list_seeded_dev.argtypes = [fp, sp, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_seeded_part_dev.argtypes = [fp, sp, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_seeded_copy_dev.argtypes = [fp, fp, sp, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_seeded_copy8_dev.argtypes = [fp, fp, sp, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
+    lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
+    lib.vfgs_hip_get_seeded_stream_stats.restype = None
     lib.vfgs_hip_get_seed_state.argtypes = [vp]
     lib.vfgs_hip_get_luts.argtypes = [i, vp, vp]
     lib.vfgs_hip_get_params.argtypes = [vp]
@@ -167,6 +175,8 @@ EXPORTS = [
     "vfgs_hip_last_error_string", "vfgs_hip_timer_begin", "vfgs_hip_timer_end", "vfgs_hip_device_info",
     "vfgs_hip_dev_build", "vfgs_hip_init_devices", "vfgs_hip_overlap_begin", "vfgs_hip_overlap_end", "vfgs_hip_get_stream_stats", "vfgs_hip_line_lookahead", "vfgs_hip_declare_frame",
     "vfgs_hip_get_stripe_stream_stats", "vfgs_hip_lfsr_segments",
+    "vfgs_hip_add_grain_frame_list_seeded_dev", "vfgs_hip_add_grain_frame_list_seeded_part_dev", "vfgs_hip_add_grain_frame_list_seeded_copy_dev",
+    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
 ]
@@ -269,6 +279,45 @@ class VfgsHip:
         assert len(src) == len(dst)
         self._ck(self.lib.vfgs_hip_add_grain_frame_list_copy8_dev(self.frame_list(src), self.frame_list(dst), len(src), width, height,
                                                                   stride, cstride, dstride, dcstride, stream))
+
+    @staticmethod
+    def seed_list(seeds):
+        """seeds: sequence of integers (what vfgs_set_seed would get, one per frame) -> ctypes uint32 array; None stays NULL."""
+        if seeds is None or isinstance(seeds, C.Array):
+            return seeds
+        return (C.c_uint32 * len(seeds))(*[int(s) & 0xFFFFFFFF for s in seeds])
+
+    def add_grain_frame_list_seeded_dev(self, frames, seeds, width, height, stride, cstride, stream=0):
+        """The list call with a seed per picture: vfgs_set_seed(seeds[f]) + frame f, for every f, in one launch per 32 frames."""
+        assert seeds is None or len(seeds) == len(frames)
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_seeded_dev(self.frame_list(frames), self.seed_list(seeds), len(frames), width, height,
+                                                                   stride, cstride, stream))
+
+    def add_grain_frame_list_seeded_part_dev(self, frames, seeds, width, frame_height, part_y, part_height, stride, cstride, stream=0):
+        assert seeds is None or len(seeds) == len(frames)
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_seeded_part_dev(self.frame_list(frames), self.seed_list(seeds), len(frames), width, frame_height,
+                                                                        part_y, part_height, stride, cstride, stream))
+
+    def add_grain_frame_list_seeded_copy_dev(self, src, dst, seeds, width, height, stride, cstride, stream=0):
+        assert len(src) == len(dst) and (seeds is None or len(seeds) == len(src))
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_seeded_copy_dev(self.frame_list(src), self.frame_list(dst), self.seed_list(seeds), len(src),
+                                                                        width, height, stride, cstride, stream))
+
+    def add_grain_frame_list_seeded_copy8_dev(self, src, dst, seeds, width, height, stride, cstride, dstride, dcstride, stream=0):
+        assert len(src) == len(dst) and (seeds is None or len(seeds) == len(src))
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_seeded_copy8_dev(self.frame_list(src), self.frame_list(dst), self.seed_list(seeds), len(src),
+                                                                         width, height, stride, cstride, dstride, dcstride, stream))
+
+    def seed_segments(self, seeds, first_bit, seg_words):
+        """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
+        out = (C.c_uint32 * (len(seeds) * seg_words))()
+        self._ck(self.lib.vfgs_hip_seed_segments(self.seed_list(seeds), len(seeds), first_bit, seg_words, out))
+        return [list(out[f * seg_words:(f + 1) * seg_words]) for f in range(len(seeds))]
+
+    def seeded_stream_stats(self):
+        out = (C.c_uint64 * 4)()
+        self.lib.vfgs_hip_get_seeded_stream_stats(out)
+        return {"images_built": out[0], "image_words": out[1], "host_waits": out[2], "last_launch_used_it": bool(out[3])}
 
     def seed_state(self):
         out = (C.c_uint32 * 4)()
