@@ -67,7 +67,7 @@ def expect_from(f: T.Frame, fi: T.Frame, out: T.Frame, legal: bool):
     samples, number of excluded samples)."""
     bs = f.depth - 8
     lo, hi = ((16 << bs), (240 << bs)) if legal else (0, (255 << bs))
-    bounds = np.array([0, (1 << f.depth) - 1, 16 << bs, 240 << bs])
+    bounds = np.array([0, (1 << f.depth) - 1, 16 << bs, 240 << bs, 255 << bs])      # (255 << bs: the full range's upper limit, below 2^depth - 1 above 8 bit)
     want = f.copy()
     want.Y[...] = out.Y
     masks, excluded = [], 0
