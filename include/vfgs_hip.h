@@ -234,6 +234,41 @@ int vfgs_hip_add_grain_frame_list_seeded_copy_dev(const vfgs_hip_frame_ptrs* src
 int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
                                                    unsigned nframes, unsigned width, unsigned height, unsigned stride, unsigned cstride,
                                                    unsigned dst_stride, unsigned dst_cstride, void* stream);
+
+/* SEMI-PLANAR frames: what a hardware decoder hands out.  A frame is a luma plane plus ONE plane of interleaved Cb/Cr pairs -- NV12 /
+ * NV16 at 8 bit, P010 / P210 / P012 at 10 and 12 bit, where the samples sit in the HIGH bits of their 16-bit containers.  One call for
+ * in place and out of place, one seed sequence and a seed per picture:
+ *   Y            a luma plane exactly as in the lists above;
+ *   UV           ceil(height / csuby) rows of Cb0 Cr0 Cb1 Cr1 ... in the depth's container (uint8 at depth 8, uint16 at 10 and 12);
+ *   stride, uv_stride   containers of a Y row / a UV row, each >= 16 * ceil(width / 16): a UV row of whole blocks is as many containers
+ *                as the luma row (whole 16-sample blocks are written, as everywhere); pointers 16-byte aligned, pitches in bytes
+ *                multiples of 16;
+ *   sample_shift 0 (low-aligned samples), or 16 - depth: P010 6, P012 4;
+ *   seeds        NULL: one seed sequence, frame f + 1 continues frame f's registers; else `nframes` values as in the seeded lists above;
+ *   src == dst (the same list, or dst[f]'s plane == src[f]'s plane) is in place.
+ * The chroma format is the programmed one and must have csubx == 2: 4:2:0 gives NV12 / P010 / P012, 4:2:2 gives NV16 / P210.
+ * With D(p) the planar, low-aligned picture of a semi-planar picture p (U = the even containers of UV, V = the odd ones, every container
+ * >> sample_shift) the samples written are those of vfgs_hip_add_grain_frame_list[_seeded]_copy_dev on D(src[f]), interleaved again, every
+ * written container << sample_shift (its low sample_shift bits zero); the four seed registers afterwards are that call's.  The low bits
+ * of a SOURCE container are ignored; with sample_shift == 0 a container above the depth's range wraps exactly as in the planar calls
+ * (vfgs_set_depth).  Bytes outside the whole blocks of a row and rows outside the picture are never written, in place or out of place.
+ * One launch per 32 frames (vfgs_hip_last_launch_info().kernel: grain_sp_kernel<depth,csuby,oney,onec>); inside an overlap region the
+ * call alternates over the two internal streams like every other device-pointer call.
+ * Refused before anything changes (a refused call does not reseed): everything the list calls above refuse, with the same codes -- a null
+ * list or plane 18, a misaligned pointer 7, bad geometry, destination planes that share bytes 18 (a UV plane that overlaps another
+ * frame's Y included), a source plane that shares bytes with another frame's destination 18 -- and, error 40 with a message that names
+ * the cause: csubx != 2; sample_shift not in {0, 16 - depth}, or non-zero at depth 8; width > 8192 (rows walked in parts); an active
+ * chroma mix (its kernels read planar chroma).  An empty list is no call at all.
+ * Out of scope, on purpose: stripe / part forms, the narrowed 8-bit destination, host-memory entry points, 4:4:4 semi-planar,
+ * persistent luma workgroups. */
+typedef struct vfgs_hip_sp_frame { void* Y; void* UV; } vfgs_hip_sp_frame;
+int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
+                                         const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
+                                         unsigned nframes, unsigned width, unsigned height,
+                                         unsigned stride, unsigned uv_stride,   /* in samples (container elements) of a Y row / a UV row */
+                                         unsigned sample_shift,      /* 0, or 16 - depth: samples sit in the high bits (P010: 6, P012: 4) */
+                                         void* stream);
+
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).
  * `out` holds nseg * seg_words 32-bit words.  first_bit is reached by one jump (a 32 x 32 bit matrix, log2(first_bit) squarings),

@@ -1442,7 +1442,8 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
                unsigned frame_y, unsigned frame_h, unsigned part_y, unsigned part_h, unsigned stride, unsigned cstride,
                unsigned nframes, uint64_t ypitch, uint64_t cpitch, hipStream_t stream, DstGeom dg = DstGeom(),
                const vfgs::FrameTable* list = nullptr,     // list: the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
-               const uint32_t* seeds = nullptr)            // seeds: frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
+               const uint32_t* seeds = nullptr,            // seeds: frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
+               const int sp_shift = -1)                    // >= 0: semi-planar frames (sU == sV, dU == dV: the UV plane, cstride its row in containers), samples that many bits up
 {
 	State& s = S();
 	if (list && nframes > (unsigned)vfgs::kListFrames) return fail(19, "internal: a listed launch holds at most %d frames", vfgs::kListFrames);
@@ -1461,6 +1462,9 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
 	}
 	if (seeds && (frame_y != 0 || !list)) return fail(19, "internal: seeds belong to lists of frames that begin at line 0");
+	const bool sp = sp_shift >= 0;
+	if (sp && (!list || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
+		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) return 0;
 	if (int e = check_luts(s)) return e;     // before any state moves: a refused call leaves the seed registers alone
@@ -1495,6 +1499,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
 	const bool mix = mix_active();
+	if (mix && sp) return fail(19, "internal: semi-planar frames with an active chroma mix");
 	if (mix && s.bs == 4)
 		return fail(38, "a chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit");
 	if (mix && !(form_one_y && form_one_c))
@@ -1513,11 +1518,13 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			d.dpitch = dg.out8 ? (pt ? dg.cstride : dg.stride) : d.pitch;
 			d.fpitch = pt ? cpitch : ypitch;
 			d.dfpitch = dg.out8 ? (pt ? dg.cpitch : dg.ypitch) : d.fpitch;
-			d.rowbytes = nblk * bw * sz;
+			// (semi-planar frames: "chroma" is the one plane of interleaved Cb/Cr pairs, a row of whole blocks as many containers as a luma row)
+			d.rowbytes = nblk * bw * sz * ((sp && pt) ? 2 : 1);
 			d.drowbytes = dg.out8 ? nblk * bw : d.rowbytes;
 			d.nrows = pt ? (int)((part_y + part_h + suby - 1) / suby) - (int)((part_y + suby - 1) / suby) : (int)part_h;
 			auto lg = [](int v) { int l = 0; while ((1 << l) < v) l++; return l; };
-			const int units = (int)((d.rowbytes + 15) / 16);       // (8-bit 4:2:x rows of an odd number of blocks end in half a unit)
+			const int ub = (sp && pt) ? vfgs::kSpUnitBytes : 16;   // (a lane's unit of an interleaved row: 32 bytes, vfgs_kernel.hip "UV walk")
+			const int units = (int)((d.rowbytes + ub - 1) / ub);   // (8-bit 4:2:x rows of an odd number of blocks end in half a unit)
 			d.rw_segs = (units + 1 + vfgs::kMaxUnits - 1) / vfgs::kMaxUnits;
 			int rpw = 1;
 			// (8-bit luma in the general form -- per-sample pattern selection, 24 LDS instructions per position -- does better with
@@ -1530,7 +1537,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			d.rw_splits = std::max<int>(1, (int)rpb / (vfgs::kWavesPerWG * rpw));
 			d.rw_lsplits = lg(d.rw_splits);
 			d.wgs = d.nrows > 0 ? nbr_stripe * d.rw_splits : 0;
-			waves += (long)(pt ? 2 : 1) * d.wgs * vfgs::kWavesPerWG * nframes;
+			waves += (long)((pt && !sp) ? 2 : 1) * d.wgs * vfgs::kWavesPerWG * nframes;
 		}
 		const long slots = (long)s.cu_count * 16;          // wave slots of the chip at the kernels' occupancy
 		if (pass < 2 && waves * 100 < VFGS_RW_MIN_FILL_PCT * slots && (a.pd[0].rw_rpw > 1 || a.pd[1].rw_rpw > 1)) { rw_shrink++; continue; }
@@ -1623,7 +1630,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	}
 
 	// one workgroup per (frame, plane, block row, part of it), numbered in memory order
-	const long per_frame = (long)a.pd[0].wgs + 2L * a.pd[1].wgs;
+	const long per_frame = (long)a.pd[0].wgs + (sp ? 1L : 2L) * a.pd[1].wgs;     // (semi-planar frames: one UV workgroup serves Cb and Cr)
 	if (per_frame > 0x3fffffffL || nframes > 65535) return fail(14, "launch too large");
 	if (per_frame == 0) { if (seeds) seeded_done(); return 0; }
 	// General-form luma of small pictures: a workgroup stages 36 KB of tables for 15-30 KB of samples.  Where a launch holds several
@@ -1633,7 +1640,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	long grid = per_frame;
 	// (10 and 12 bit -- the same bytes through the same LDS image -- only: at 8 bit the general-form kernels are bound by their LDS instructions, and confining luma to P < all workgroup
 	// slots costs them 7 %; at 10 bit 1080p gains 6 % at 32 and 64 frames per launch, 2160p nothing: profiles/r04_ab2_persistent_luma.log)
-	if (VFGS_PERSIST_MIN_TASKS > 0 && s.bs != 0 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
+	if (VFGS_PERSIST_MIN_TASKS > 0 && !sp && s.bs != 0 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
 	    (size_t)vfgs::kWavesPerWG * a.pd[0].rw_rpw * a.pd[0].rowbytes <= ((size_t)VFGS_PERSIST_MAX_WG_KB << 10))
 	{
 		const long tasks = (long)a.pd[0].wgs * nframes, slots = (long)s.cu_count * 4;     // (general form: four workgroups per CU)
@@ -1655,7 +1662,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 #else
 	// (not inside an overlap region: there the second sweep is the launch on the other stream, and four fronts lose 15 %)
 	const bool in_region = g_states[0].ov.active && (stream == g_states[0].ov.s[0] || stream == g_states[0].ov.s[1]);
-	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + 2 * cext) >= (64u << 20)) ? 1 : 0;
+	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + (sp ? 1 : 2) * cext) >= (64u << 20)) ? 1 : 0;
 #endif
 	if (mix)
 	{
@@ -1686,6 +1693,11 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, true, true, wide, false, (int)grid, stream));
 			a.mix_planes = 2;      // luma only
 		}
+	}
+	if (sp)
+	{
+		a.sp_kernel = 1;
+		a.sp_shift2 = (uint32_t)sp_shift * 0x10001u;
 	}
 	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist, (int)grid, stream));
 	if (seeds) seeded_done();
@@ -1723,6 +1735,12 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			li.lds_bytes_per_workgroup = vfgs::mix_lds_allocation(L.lds_bytes + vfgs::kParamBytes);
 			snprintf(li.kernel, sizeof li.kernel, "grain_mix_kernel<%d,%d,%d,%s,%s>", 8 + s.bs, s.csubx, s.csuby, dg.out8 ? "true" : "false", wide ? "true" : "false");
 			if (a.mix_planes) li.launches++;
+		}
+		if (sp)
+		{
+			// (the kernels of semi-planar frames: depth, chroma subsampling y, one-pattern luma, one-pattern chroma; "chroma" in the per-plane figures is the UV plane)
+			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, s.img_one_c));
+			snprintf(li.kernel, sizeof li.kernel, "grain_sp_kernel<%d,%d,%s,%s>", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false", s.img_one_c ? "true" : "false");
 		}
 		g_last_launch_valid = true;
 	}
@@ -2883,8 +2901,11 @@ int vfgs_hip_add_grain_frames_part_dev(void* dY, void* dU, void* dV, unsigned wi
 // kListFrames frames whose plane pointers travel in the kernel arguments.
 static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, unsigned nframes, unsigned width, unsigned height,
                           unsigned stride, unsigned cstride, hipStream_t stream, DstGeom dg, bool whole = true, unsigned part_y = 0, unsigned part_h = 0,
-                          bool seeded = false, const uint32_t* seeds = nullptr)     // seeded: frame f is the frame behind vfgs_set_seed(seeds[f])
+                          bool seeded = false, const uint32_t* seeds = nullptr,     // seeded: frame f is the frame behind vfgs_set_seed(seeds[f])
+                          const int sp_shift = -1)     // >= 0: semi-planar frames, U == V == the UV plane of a frame and cstride its row (run_device)
 {
+	const bool sp = sp_shift >= 0;
+	const int ncomp = sp ? 2 : 3;     // planes of a frame
 	if (whole) { part_y = 0; part_h = height; }
 	State& s = S();
 	if (int e = ensure_init(-1)) return e;
@@ -2897,6 +2918,8 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride)) return e;
 		if ((((uintptr_t)dst[f].Y | (uintptr_t)dst[f].U | (uintptr_t)dst[f].V) & 15)) return fail(7, "plane pointers must be 16-byte aligned");
 	}
+	if (sp && cstride < (width + 15) / 16 * 16)
+		return fail(6, "uv_stride %u too small: whole 16-sample blocks of Cb/Cr pairs are written (need >= %u)", cstride, (width + 15) / 16 * 16);
 	// The frames run concurrently: destination planes that overlap (the same plane listed twice, or two that share bytes) would be
 	// a race where consecutive calls are not, and so would a source plane of one frame that shares bytes with the destination of
 	// ANOTHER (that frame may already have been grained when it is read).  The bytes of a plane: its rows of the stripe, whole
@@ -2906,15 +2929,16 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 		const uint64_t crows = part_h ? (uint64_t)(part_y + part_h - 1) / s.csuby - part_y / s.csuby + 1 : 0;
 		const uint64_t dsz = dg.out8 ? 1 : sz, dstr = dg.out8 ? dg.stride : stride, dcstr = dg.out8 ? dg.cstride : cstride;
 		auto extent = [&](uint64_t rows, uint64_t pitch, uint64_t rowb) { return rows ? (rows - 1) * pitch + rowb : 0; };
-		const uint64_t ext_s[3] = {extent(part_h, stride * sz, nblk * 16 * sz), extent(crows, cstride * sz, nblk * 16 / s.csubx * sz), 0};
-		const uint64_t ext_d[3] = {extent(part_h, dstr * dsz, nblk * 16 * dsz), extent(crows, dcstr * dsz, nblk * 16 / s.csubx * dsz), 0};
+		const uint64_t cblk = sp ? 16 : 16 / s.csubx;     // containers of a grain block in a chroma row (semi-planar: Cb and Cr)
+		const uint64_t ext_s[3] = {extent(part_h, stride * sz, nblk * 16 * sz), extent(crows, cstride * sz, nblk * cblk * sz), 0};
+		const uint64_t ext_d[3] = {extent(part_h, dstr * dsz, nblk * 16 * dsz), extent(crows, dcstr * dsz, nblk * cblk * dsz), 0};
 		struct Span { uintptr_t lo, hi; unsigned frame; };
 		std::vector<Span> d;
 		d.reserve(3 * (size_t)nframes);
 		for (unsigned f = 0; f < nframes; f++)
 		{
 			const void* pl[3] = {dst[f].Y, dst[f].U, dst[f].V};
-			for (int c = 0; c < 3; c++) d.push_back({(uintptr_t)pl[c], (uintptr_t)pl[c] + ext_d[c ? 1 : 0], f});
+			for (int c = 0; c < ncomp; c++) d.push_back({(uintptr_t)pl[c], (uintptr_t)pl[c] + ext_d[c ? 1 : 0], f});
 		}
 		std::sort(d.begin(), d.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
 		for (size_t i = 1; i < d.size(); i++)
@@ -2925,7 +2949,7 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 		{
 			const void* pl[3] = {src[f].Y, src[f].U, src[f].V};
 			const void* own[3] = {dst[f].Y, dst[f].U, dst[f].V};
-			for (int c = 0; c < 3; c++)
+			for (int c = 0; c < ncomp; c++)
 			{
 				const uintptr_t lo = (uintptr_t)pl[c], hi = lo + ext_s[c ? 1 : 0];
 				// destinations are disjoint and sorted: the first one that ends behind lo is the only candidate below hi ... and its successors
@@ -2947,7 +2971,7 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			ft.dst[0][k] = (uint8_t*)b.Y; ft.dst[1][k] = (uint8_t*)b.U; ft.dst[2][k] = (uint8_t*)b.V;
 		}
 		if (int e = run_device(src[f0].Y, src[f0].U, src[f0].V, dst[f0].Y, dst[f0].U, dst[f0].V, width, 0, height, part_y, part_h, stride, cstride,
-		                       n, 0, 0, stream, dg, &ft, seeded ? seeds + f0 : nullptr))
+		                       n, 0, 0, stream, dg, &ft, seeded ? seeds + f0 : nullptr, sp_shift))
 			return e;
 	}
 	return 0;
@@ -3030,6 +3054,36 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
 	dg.out8 = true;
 	dg.stride = dst_stride; dg.cstride = dst_cstride;
 	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), dg, true, 0, 0, true, seeds);
+}
+
+// Semi-planar frames (vfgs_hip.h): a luma plane and ONE plane of interleaved Cb/Cr pairs per frame.  What this call alone refuses is
+// refused here, before anything moves; the list then is a frame list whose U and V planes are the UV plane (run_frame_list, run_device).
+int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
+                                         unsigned width, unsigned height, unsigned stride, unsigned uv_stride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	if (s.csubx != 2)
+		return fail(40, "semi-planar frames: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
+	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
+		return fail(40, "semi-planar frames: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
+	if (width > (unsigned)vfgs::kTileBlocks * 16)
+		return fail(40, "semi-planar frames: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
+	if (mix_active())
+		return fail(40, "semi-planar frames: a chroma mix is active (the kernels of the mix read planar chroma)");
+	if (!src || !dst) return fail(18, "frame list: null list");
+	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd;
+	for (unsigned f = 0; f < nframes; f++) ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};
+	if (src != dst)
+	{
+		pd.resize(nframes);
+		for (unsigned f = 0; f < nframes; f++) pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
+	}
+	return run_frame_list(ps.data(), src != dst ? pd.data() : ps.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), DstGeom(), true, 0, 0,
+	                      seeds != nullptr, seeds, (int)sample_shift);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,

@@ -26,7 +26,10 @@
 //   * rows of more than 512 grain blocks (8192 luma samples) are walked in parts of 512 blocks, the parameter table refilled
 //     between the parts; the 8-bit output of a 10- or 12-bit path (yuv.c:216-258) is a narrowing in the store (OUT8 kernels);
 //   * the frames of a launch lie at a constant pitch behind the plane pointers of the arguments, or anywhere: then their plane
-//     pointers are a table IN the kernel arguments (FrameTable, vfgs_layout.h) and a workgroup reads its frame's with scalar loads.
+//     pointers are a table IN the kernel arguments (FrameTable, vfgs_layout.h) and a workgroup reads its frame's with scalar loads;
+//   * semi-planar frames (a luma plane + ONE plane of interleaved Cb/Cr pairs, samples possibly in the high bits of their containers) have a
+//     kernel family of their own, grain_sp_kernel: the luma walk with a container shift, and a UV walk whose lanes move 32 bytes and split
+//     them into one planar Cb unit and one planar Cr unit ("UV walk" below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -119,6 +122,19 @@ __device__ __forceinline__ int mad_i32_i16(int x, uint32_t y, int c)
 __device__ __forceinline__ int dot2_i16(uint32_t a, uint32_t b, int c)
 {
 	return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), c, false);
+}
+// both 16-bit halves shifted by the corresponding half of `sh` (semi-planar frames: samples in the high bits of their containers)
+__device__ __forceinline__ uint32_t pk_lshr_b16(uint32_t sh, uint32_t v)
+{
+	uint32_t r;
+	asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "s"(sh), "v"(v));
+	return r;
+}
+__device__ __forceinline__ uint32_t pk_lshl_b16(uint32_t sh, uint32_t v)
+{
+	uint32_t r;
+	asm("v_pk_lshlrev_b16 %0, %1, %2" : "=v"(r) : "s"(sh), "v"(v));
+	return r;
 }
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b)      // mask ? a : b, bit by bit
 {
@@ -658,7 +674,9 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     lane's chroma unit -- same descriptors-per-group scheme, so they are 16-byte coalesced and range-checked against the luma row, and
 //     issued with the position's own sample loads: they are part of the ring, which is two sets deep here -- forms the index dwords in
 //     the unit's layout (mix_index) and sends them through the same lane shift as the samples.
-template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false>
+//   * SP (luma planes of grain_sp_kernel, 16-bit containers): the samples sit KernelArgs::sp_shift2 bits up in their containers; a position's
+//     units are shifted down as they leave the ring and the results up before they go to memory (a packed 16-bit shift per dword each way).
+template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, bool SP = false>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
 {
@@ -685,6 +703,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(IMG_BYTES % 16 == 0, "table image in whole 16-byte units");
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
+	static_assert(!SP || (NARROW == 0 && !OUT8 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk");
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
@@ -693,6 +712,8 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	// of samples it serves) runs several tasks with ONE staging of the image: only the block parameters are per task (their
 	// LFSR words and the task's first four positions are requested before the workgroup meets at the barrier that frees the
 	// parameter table).
+	// (run_uv_sp below restates the placement, the LFSR loads, the parameter-table fill and the group / descriptor logic of this lambda for the
+	// interleaved UV plane of semi-planar frames: a fix here belongs there too)
 	auto task = [&](const int f, const int r, const bool first_task) {
 	// ---- the workgroup's place: block row of the stripe, part of it; the wave's rows -------------------------------
 	const int split = r & (pd.rw_splits - 1);
@@ -1017,6 +1038,11 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				// assemble my 16 bytes: the last K dwords of the unit of the lane before me, the first 4 - K of mine
 				uint32_t t[4];
 				uint32_t ti[4] = {};
+				if constexpr (SP && DEPTH > 8)
+				{
+#pragma unroll
+					for (int d = 0; d < 4; d++) w[u][d] = pk_lshr_b16(a.sp_shift2, w[u][d]);
+				}
 				if constexpr (MIX)
 				{
 					// index dwords of my memory unit, then the same lane shift as the samples
@@ -1076,6 +1102,11 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				}
 				uint32_t o[DW];
 				results(t, o);
+				if constexpr (SP && DEPTH > 8)
+				{
+#pragma unroll
+					for (int d = 0; d < DW; d++) o[d] = pk_lshl_b16(a.sp_shift2, o[d]);
+				}
 				// the previous position's units are complete once the KD dwords its lanes computed have moved one lane down; its
 				// lane 63 takes them from my lane 0 (the previous position of a row's first one is the last of another row:
 				// its lane 63 lies behind that row's end and is never stored)
@@ -1244,6 +1275,301 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 }
 
 // ---------------------------------------------------------------------------------------
+// UV walk: semi-planar frames (NV12, NV16, P010, P210, P012; vfgs_hip_add_grain_sp_frame_list_dev).
+//
+// The chroma of such a frame is ONE plane of interleaved Cb/Cr pairs.  A UV workgroup takes the place of the row walk's Cb workgroup
+// and its Cr workgroup: the same rows of one block row, a wave owns whole UV rows, and
+//   * a lane's memory unit is 32 bytes (two 16-byte buffer loads, a wave access is 2 KiB), split in registers with v_perm_b32 into one
+//     planar Cb unit and one planar Cr unit -- shifted down where the samples sit in the high bits of their containers -- each exactly
+//     what a lane of the planar chroma walk holds: the lane shift (DPP), the hand-over between positions, the edge filter and grain_unit
+//     run on them unchanged, once with Cb's block parameters and tables, once with Cr's; the two result units are shifted up,
+//     interleaved again and stored as 32 bytes, one position behind their load like every unit of the row walk;
+//   * the workgroup stages both components' tables (vfgs_layout.h "semi-planar"), and computes both components' block parameters from
+//     ONE load of the block row's LFSR words: Cb and Cr take different bit fields of the same register (block_param);
+//   * row ends are the buffer descriptor's range check, per dword: an 8-bit row of an odd number of blocks ends in half a 32-byte unit;
+//   * rows are at most kTileBlocks blocks (the host refuses wider pictures): one parameter table per component and block row.
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG>
+__device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
+{
+	constexpr int NS = DEPTH == 8 ? 16 : 8;
+	constexpr int SZ = DEPTH > 8 ? 2 : 1;
+	constexpr int SB = ONE ? ((DEPTH == 8 && kPk16) ? 2 : 1) : kSlots;
+	constexpr int BW = 8;                                // chroma samples of a grain block (csubx == 2)
+	using M = LaneMap<NS, BW>;
+	static_assert(!M::PAIR, "a lane of a horizontally subsampled plane holds whole half blocks");
+	constexpr int NR = M::NR, NE = M::NE;
+	constexpr int RPB = 16 / SUBY;
+	constexpr int K = M::SHIFT * SZ / 4;                 // dwords of a planar unit that belong to the lane before its own
+	constexpr int BPS = 64 * M::BPL;                     // grain blocks a position advances by
+	constexpr int NU = kSpRing;
+	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
+	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
+	constexpr int IMG = sp_uv_image_bytes(CIMG, LUTB, ONE);
+	constexpr uint32_t BANK_OFF = ONE ? BANK : BANK + LUTB;     // of the bank behind a component's base (general form: behind BOTH pairs of tables)
+	constexpr uint32_t PT = IMG;                         // parameter tables: component c, this block row at PT + 2 c tables, the row above one further
+	static_assert(IMG % 16 == 0 && CIMG % 16 == 0, "table images in whole 16-byte units");
+	static_assert(kTileBlocks % (NU * BPS) == 0 || NU * BPS > kTileBlocks, "positions of whole blocks");
+	const PlaneDesc& pd = a.pd[1];
+	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+
+	// ---- the workgroup's place (run_plane_rw "task") ----------------------------------------------------------------
+	const int split = r & (pd.rw_splits - 1);
+	const int kbr = uni(r >> pd.rw_lsplits);
+	const int Rabs = (a.y0 >> 4) + kbr;
+	const int row_first = (a.y0 + SUBY - 1) / SUBY;
+	const int prow0 = a.y0 / SUBY;
+	const int alo = max(row_first, Rabs * RPB), ahi = min(row_first + pd.nrows, (Rabs + 1) * RPB);
+	const int rpw = pd.rw_rpw;
+	constexpr int RSTR = kWavesPerWG;
+	const int base = uni(Rabs * RPB + split * (kWavesPerWG * rpw) + wave);
+	int k0 = (max(0, alo - base) + kWavesPerWG - 1) / kWavesPerWG, k1 = min(rpw, (max(0, ahi - base) + kWavesPerWG - 1) / kWavesPerWG);
+	if (kbr >= a.nbrows || k1 < k0) k1 = k0;
+	k0 = uni(k0); k1 = uni(k1);
+	const bool wg_up = (Rabs > 0) && (split == 0);
+
+	const int last = a.nblk - 1;
+	const uint32_t cur_bit = a.cur_bit0 + (uint32_t)f * a.frame_bit_step + (uint32_t)(kbr * a.nblk);
+	const uint32_t up_bit = (kbr > 0) ? cur_bit - (uint32_t)a.nblk : a.up_bit0 + (uint32_t)f * a.frame_bit_step;
+
+	// ---- in flight together: the tables, the LFSR words of the row's blocks, my first positions ------------------------
+	constexpr int STEP = kWavesPerWG * 64 * 16;
+	constexpr int NIT = (IMG + STEP - 1) / STEP;
+	u32x4 tmp[NIT];
+	{
+		// (the device image holds [LUT Cb][bank][LUT Cr][bank]: one-pattern form -- both sub-images as they are; general form -- LDS offset o
+		// comes from Cb's LUT, Cr's LUT, Cb's copy of the bank)
+		const __amdgpu_buffer_rsrc_t irs = make_rsrc(a.tables + img_off, 2 * CIMG);
+#pragma unroll
+		for (int it = 0; it < NIT; it++)
+		{
+			const uint32_t o = min((uint32_t)(threadIdx.x * 16 + it * STEP), (uint32_t)(IMG - 16));
+			const uint32_t so = ONE ? o : (o < (uint32_t)LUTB ? o : (o < 2u * LUTB ? o - LUTB + CIMG : o - LUTB));
+			tmp[it] = __builtin_amdgcn_raw_buffer_load_b128(irs, so, 0, 0);
+		}
+	}
+	constexpr int NPE = (kParamEntries + kWavesPerWG * 64 - 1) / (kWavesPerWG * 64);
+	const __amdgpu_buffer_rsrc_t strs = make_rsrc((const uint8_t*)a.stream, a.stream_bytes);
+	const __amdgpu_buffer_rsrc_t strs_up = make_rsrc((const uint8_t*)a.stream, wg_up ? a.stream_bytes : 0);
+	u32x2 wc[NPE], wu[NPE];
+#pragma unroll
+	for (int i = 0; i < NPE; i++)
+	{
+		const int e = (int)threadIdx.x + i * kWavesPerWG * 64;
+		const uint32_t blk = (uint32_t)min(max(e - 1, 0), last);
+		const bool need = e < a.nblk + 4 && e < kParamEntries;
+		wc[i] = __builtin_amdgcn_raw_buffer_load_b64(strs, need ? ((cur_bit + blk) >> 5) * 4 : kOOB, 0, 0);
+		wu[i] = __builtin_amdgcn_raw_buffer_load_b64(strs_up, need ? ((up_bit + blk) >> 5) * 4 : kOOB, 0, 0);
+	}
+	const int tsegs = pd.rw_segs;
+	const int ngroups = (tsegs + NU - 1) / NU;
+	const uint8_t* sbase = a.listed ? ft.src[1][f] : a.src[1] + (uint64_t)f * pd.fpitch;
+	uint8_t* dbase = a.listed ? ft.dst[1][f] : a.dst[1] + (uint64_t)f * pd.dfpitch;
+	const uint32_t lane32 = (uint32_t)lane * kSpUnitBytes;
+	constexpr uint32_t UB = kMaxUnits * kSpUnitBytes;    // bytes of a position
+	constexpr uint32_t GB = NU * UB;                     // ... of a group
+	auto row_off = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.pitch); };
+	auto left = [&](int g) { const uint32_t o = (uint32_t)g * GB; return o < pd.rowbytes ? min(pd.rowbytes - o, GB) : 0u; };
+	uint32_t w[NU][8];
+	auto load_pos = [&](const __amdgpu_buffer_rsrc_t rs, const int u) {
+		const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB, 0, LDA);
+		const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB + 16, 0, LDA);
+		w[u][0] = lo.x; w[u][1] = lo.y; w[u][2] = lo.z; w[u][3] = lo.w;
+		w[u][4] = hi.x; w[u][5] = hi.y; w[u][6] = hi.z; w[u][7] = hi.w;
+	};
+	{
+		const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(sbase + (k0 < k1 ? row_off(k0) : 0u), k0 < k1 ? left(0) : 0u);
+#pragma unroll
+		for (int u = 0; u < NU; u++) load_pos(rs0, u);
+	}
+#pragma unroll
+	for (int it = 0; it < NIT; it++)
+		*(u32x4*)(lds + min((uint32_t)(threadIdx.x * 16 + it * STEP), (uint32_t)(IMG - 16))) = tmp[it];
+
+	// ---- block parameters of the row, both components (once per workgroup) ---------------------------------------------
+#pragma unroll
+	for (int i = 0; i < NPE; i++)
+	{
+		if (i > 0 && i * kWavesPerWG * 64 >= a.nblk + 4) break;
+		const int e = (int)threadIdx.x + i * kWavesPerWG * 64;
+		const uint32_t blk = (uint32_t)min(max(e - 1, 0), last);
+		const uint32_t vc = __builtin_amdgcn_alignbit(wc[i].y, wc[i].x, (cur_bit + blk) & 31);
+		const uint32_t vu = __builtin_amdgcn_alignbit(wu[i].y, wu[i].x, (up_bit + blk) & 31);
+#pragma unroll
+		for (int c = 0; c < 2; c++)
+		{
+			const int fsx = c ? 20 : 10, fsy = c ? 4 : 24, fsb = c ? 15 : 2;      // vfgs_hw.c:99-138, components 1 and 2
+			bool neg;
+			const uint32_t pc = (block_param<2, SUBY, RS, SB>(vc, BANK_OFF, fsx, fsy, fsb, &neg) + ((ONE && neg) ? (uint32_t)NEG : 0u)) | (neg ? 0x80000000u : 0u);
+			const uint32_t pu = block_param<2, SUBY, RS, SB>(vu, BANK_OFF, fsx, fsy, fsb, &neg) | (neg ? 0x80000000u : 0u);
+			if (e < kParamEntries)
+			{
+				*(uint32_t*)(lds + PT + (2 * c) * kParamTableBytes + e * 4) = pc;
+				*(uint32_t*)(lds + PT + (2 * c + 1) * kParamTableBytes + e * 4) = pu;
+			}
+		}
+	}
+	__syncthreads();
+	if (k0 >= k1)
+		return;
+
+	// ---- per lane constants ------------------------------------------------------------------------------------------
+	const uint32_t lo2 = a.lo2[1], hi2 = a.hi2[1];
+	const uint32_t idx0 = (uint32_t)lane * M::BPL * 4;
+	const int cl = lane * M::BPL - 1;
+	auto lane_up = [](uint32_t old, uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xf, 0xf, false); };    // wave_shr:1
+	auto lane_down = [](uint32_t old, uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xf, 0xf, false); };  // wave_shl:1
+	auto rot_up = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x13c, 0xf, 0xf, false); };      // wave_ror:1
+	auto rot_down = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x134, 0xf, 0xf, false); };    // wave_rol:1
+	// byte selectors of the split (a dword pair of the UV row -> one dword of Cb, one of Cr) and of the interleave (one of each -> the pair)
+	constexpr uint32_t SPLIT_CB = SZ == 2 ? 0x05040100u : 0x06040200u, SPLIT_CR = SZ == 2 ? 0x07060302u : 0x07050301u;
+	constexpr uint32_t JOIN_LO = SZ == 2 ? 0x05040100u : 0x05010400u, JOIN_HI = SZ == 2 ? 0x07060302u : 0x07030602u;
+
+	// ---- the walk ----------------------------------------------------------------------------------------------------
+	uint32_t carry[2][K];                  // in lane 0: the last K dwords of lane 63 of the previous position of the row, per component
+	uint32_t outp[2][4] = {};              // the previous position's planar units: dwords K.. of its lanes
+	uint32_t tp[2][K] = {};                // ... and the first K dwords its lanes computed: they belong one lane down
+#pragma unroll
+	for (int c = 0; c < 2; c++)
+#pragma unroll
+		for (int d = 0; d < K; d++) carry[c][d] = 0;
+	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);
+	// the previous position is complete: interleave its two planar units, shift them up, store 32 bytes
+	auto store_prev = [&](const __amdgpu_buffer_rsrc_t rs, const uint32_t off) {
+		uint32_t st[8];
+#pragma unroll
+		for (int j = 0; j < 4; j++)
+		{
+			st[2 * j] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], JOIN_LO);
+			st[2 * j + 1] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], JOIN_HI);
+		}
+		if constexpr (DEPTH > 8)
+		{
+#pragma unroll
+			for (int j = 0; j < 8; j++) st[j] = pk_lshl_b16(a.sp_shift2, st[j]);
+		}
+		const uint32_t s0[4] = {st[0], st[1], st[2], st[3]}, s1[4] = {st[4], st[5], st[6], st[7]};
+		store_unit<4, STA>(rs, lane32 + off, s0);
+		store_unit<4, STA>(rs, lane32 + off + 16, s1);
+	};
+	auto walk_row = [&](auto overlap, const int k) {
+		constexpr bool OV = decltype(overlap)::value;
+		const int j = base + RSTR * k - Rabs * RPB;    // row inside the block row
+		const int jrow = j * SUBY;
+		const uint32_t rowoff = (uint32_t)j * RS, uprowoff = (uint32_t)(RPB + j) * RS;
+		const int wc_ = jrow == 0 ? (SUBY > 1 ? 20 : 12) : 24, wu_ = jrow == 0 ? (SUBY > 1 ? 20 : 24) : 12;
+		const uint32_t ro = row_off(k);
+		for (int g = 0; g < ngroups; g++)
+		{
+			const bool lastg = g + 1 == ngroups;
+			const int ng = lastg ? 0 : g + 1;
+			const bool nvalid = !lastg || k + 1 < k1;
+			const uint32_t nso = nvalid ? (lastg ? row_off(k + 1) : ro) + (uint32_t)ng * GB : 0u;
+			const __amdgpu_buffer_rsrc_t nsrc = make_rsrc(sbase + nso, nvalid ? left(ng) : 0u);
+			const __amdgpu_buffer_rsrc_t cdst = make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
+			const uint8_t* pe = lds + idx0 + (uint32_t)(g * NU * BPS * 4);
+			const int clg = cl + g * NU * BPS;
+#pragma unroll
+			for (int u = 0; u < NU; u++)
+			{
+				const bool firsts = u == 0 && g == 0;
+				// my 32 bytes as a planar Cb unit and a planar Cr unit, low-aligned samples
+				uint32_t cw[2][4];
+#pragma unroll
+				for (int q = 0; q < 4; q++)
+				{
+					cw[0][q] = __builtin_amdgcn_perm(w[u][2 * q + 1], w[u][2 * q], SPLIT_CB);
+					cw[1][q] = __builtin_amdgcn_perm(w[u][2 * q + 1], w[u][2 * q], SPLIT_CR);
+				}
+				if constexpr (DEPTH > 8)
+				{
+#pragma unroll
+					for (int c = 0; c < 2; c++)
+#pragma unroll
+						for (int q = 0; q < 4; q++) cw[c][q] = pk_lshr_b16(a.sp_shift2, cw[c][q]);
+				}
+				// the registers are free: refill them with the position NU steps ahead
+				load_pos(nsrc, u);
+				const bool live = NU * g + u < tsegs;
+				bool edge_on[NE];
+#pragma unroll
+				for (int ed = 0; ed < NE; ed++) edge_on[ed] = (clg + u * BPS + ed >= 0) && (clg + u * BPS + ed < last);
+				uint32_t res[2][4];
+#pragma unroll
+				for (int c = 0; c < 2; c++)
+				{
+					// the component's tables: one-pattern form -- a sub-image of its own; general form -- its pair of tables in front of the shared bank
+					const uint8_t* cl_ = lds + ((ONE && c) ? CIMG : 0);
+					const uint32_t lutb = (ONE ? 0u : (uint32_t)(c * LUTB)) * 0x10001u;
+					uint32_t (&t)[4] = res[c];
+#pragma unroll
+					for (int d = 0; d < K; d++) t[d] = lane_up(firsts ? 0u : carry[c][d], cw[c][4 - K + d]);
+#pragma unroll
+					for (int d = 0; d < K; d++) carry[c][d] = rot_up(cw[c][4 - K + d]);
+#pragma unroll
+					for (int d = K; d < 4; d++) t[d] = cw[c][d - K];
+					if (live)
+					{
+						RunParam<NR> rp, up;
+#pragma unroll
+						for (int rr = 0; rr < NR; rr++) rp.pa[rr] = *(const uint32_t*)(pe + PT + (2 * c) * kParamTableBytes + (u * BPS + rr) * 4);
+#pragma unroll
+						for (int rr = 0; rr < NR; rr++) up.pa[rr] = OV ? *(const uint32_t*)(pe + PT + (2 * c + 1) * kParamTableBytes + (u * BPS + rr) * 4) : 0u;
+						grain_unit<DEPTH, BW, OV, ONE, ONE, NEG>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, t);
+					}
+#pragma unroll
+					for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(rot_down(t[d]), tp[c][d]);
+				}
+				if (u == 0) store_prev(pdst, (NU - 1) * UB);
+				else store_prev(cdst, (u - 1) * UB);
+#pragma unroll
+				for (int c = 0; c < 2; c++)
+				{
+#pragma unroll
+					for (int d = K; d < 4; d++) outp[c][d - K] = res[c][d];
+#pragma unroll
+					for (int d = 0; d < K; d++) tp[c][d] = res[c][d];
+				}
+#if VFGS_SCHED_FENCE
+				__builtin_amdgcn_sched_barrier(0);
+#endif
+			}
+			pdst = cdst;
+		}
+	};
+	for (int k = k0; k < k1; k++)
+	{
+		const int jrow = (base + RSTR * k - Rabs * RPB) * SUBY;
+		if (Rabs > 0 && jrow <= 1) walk_row(std::true_type(), k);      // blends in the block above (vfgs_hw.c:173-188, 223-229)
+		else walk_row(std::false_type(), k);
+	}
+	// the last position of my last row
+#pragma unroll
+	for (int c = 0; c < 2; c++)
+#pragma unroll
+		for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(0u, tp[c][d]);
+	store_prev(pdst, (NU - 1) * UB);
+}
+
+// The kernels of semi-planar frames (KernelArgs::sp_kernel): the grid and the workgroup numbering of grain_rw_kernel with ONE UV workgroup where
+// that has a Cb and a Cr workgroup.  kSpWgPerCU (vfgs_layout.h) workgroups per CU in every form: a UV wave keeps two components' walks alive.
+template <int DEPTH, int CSUBY, bool ONEY, bool ONEC>
+__global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp_kernel(const KernelArgs a, const FrameTable ft)
+{
+	constexpr ImageLayout L = image_layout(2, CSUBY, ONEY, ONEC, DEPTH == 8);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[sp_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, ONEC))];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	const int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	if (r < a.pd[0].wgs)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
+}
+
+// ---------------------------------------------------------------------------------------
 // host-side launcher (called from vfgs_host.cpp)
 
 template <int DEPTH, int CSUBX, int CSUBY, bool OUT8>
@@ -1310,9 +1636,29 @@ static hipError_t launch_form(const KernelArgs& a, const FrameTable& ft, bool on
 // start-up time round 5 hoped for: a code object's first launch costs 1.3 ms (profiles/r06_startup_probe_two_code_objects.jsonl), so the 15 ms
 // of a process's first grain launch are the allocations and first transfers around it, not the 88 kernels.  Without the macro (the assembly
 // listings) everything is one translation unit.
+template <int DEPTH, int CSUBY>
+static hipError_t launch_sp(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	if (oney && onec) hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
+	else if (oney) hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
+	else if (onec) hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
+	else hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
 template <int D>
 static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
 {
+	if (a.sp_kernel)
+	{
+		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table, no mix (the host refuses everything else)
+		if (a.mix_kernel || out8 || wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
+		if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
+		if (csuby == 2) return launch_sp<D, 2>(a, ft, oney, onec, grid, stream);
+		if (csuby == 1) return launch_sp<D, 1>(a, ft, oney, onec, grid, stream);
+		return hipErrorInvalidValue;
+	}
 	if (a.mix_kernel)
 	{
 		// (no mix kernels at 12 bit: launch_depth<12> instantiates none, the host refuses such a call before it gets here)

@@ -115,6 +115,29 @@ constexpr int mix_lds_allocation(const int need)
 	return need > target ? need : target;
 }
 
+// The kernels of semi-planar frames (grain_sp_kernel, vfgs_kernel.hip "UV walk"): luma workgroups are the row walk's; a UV workgroup serves
+// BOTH chroma components of its rows and holds both components' tables in LDS:
+//   one-pattern chroma : [Cb sub-image][Cr sub-image]                  (each component's +scale table and its own pattern with the negated copy)
+//   general form       : [LUT Cb: 2 x 256 dwords][LUT Cr][chroma bank] (the bank once)
+// followed by FOUR parameter tables (Cb: this block row, the row above; Cr: the same).  A lane's memory unit is 32 bytes of the
+// interleaved row, a wave access 2 KiB, and the ring holds kSpRing of them (as many bytes in flight per wave as the planar kernels' ring of four).
+constexpr int kSpRing = 2;
+constexpr int kSpWgPerCU = 4;      // resident workgroups per CU of every grain_sp_kernel: its launch bounds AND its LDS allocation (sp_lds_allocation)
+constexpr int kSpUnitBytes = 32;
+constexpr int sp_uv_image_bytes(const int c_bytes, const int lut_bytes, const bool one_c) { return one_c ? 2 * c_bytes : c_bytes + lut_bytes; }
+constexpr int sp_lds_need(const int y_bytes, const int c_bytes, const int lut_bytes, const bool one_c)
+{
+	const int y = y_bytes + kParamBytes, uv = sp_uv_image_bytes(c_bytes, lut_bytes, one_c) + 2 * kParamBytes;
+	return y > uv ? y : uv;
+}
+
+// (what a semi-planar kernel ALLOCATES: exactly kSpWgPerCU workgroups per CU, like the kernels of the mix)
+constexpr int sp_lds_allocation(const int need)
+{
+	const int target = (kLdsPerCU / kSpWgPerCU) & ~2047;
+	return need > target ? need : target;
+}
+
 // Device image of everything the kernel looks up: one sub-image per plane type (luma; chroma) -- or per chroma
 // component -- and a workgroup (which works on ONE plane) copies the sub-image of its plane to LDS offset 0.
 //
@@ -252,6 +275,9 @@ struct KernelArgs {
 	int mix_planes;           // ... bit 0: its luma workgroups do nothing, bit 1: its chroma workgroups do nothing (the two launches of an in-place call)
 	int mix_lw;               // ... luma width of the call in samples (the last luma sample of a row pairs with itself)
 	int mix[2][4];            // ... Cb, Cr: { luma_mult, chroma_mult, offset << (depth - 8), active }
+	// Semi-planar frames (vfgs_hip_add_grain_sp_frame_list_dev; all zero = the planar kernels of always)
+	int sp_kernel;            // 1: grain_sp_kernel serves the launch: components 1 and 2 are ONE plane of interleaved Cb/Cr pairs, pd[1] describes its row
+	uint32_t sp_shift2;       // ... 16-bit containers: the samples sit this many bits up (P010: 6, P012: 4), in both halves of the dword (a packed 16-bit shift each way)
 };
 
 }  // namespace vfgs

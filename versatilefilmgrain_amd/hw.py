@@ -116,6 +116,8 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_add_grain_frame_list_seeded_part_dev.argtypes = [fp, sp, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_seeded_copy_dev.argtypes = [fp, fp, sp, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_seeded_copy8_dev.argtypes = [fp, fp, sp, u, u, u, u, u, u, u, vp]
+    spf = C.POINTER(SpFrame)
+    lib.vfgs_hip_add_grain_sp_frame_list_dev.argtypes = [spf, spf, sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -161,6 +163,11 @@ class FramePtrs(C.Structure):
     _fields_ = [("Y", C.c_void_p), ("U", C.c_void_p), ("V", C.c_void_p)]
 
 
+class SpFrame(C.Structure):
+    """include/vfgs_hip.h: vfgs_hip_sp_frame (device pointers to line 0 of a semi-planar frame's luma plane and its plane of Cb/Cr pairs)."""
+    _fields_ = [("Y", C.c_void_p), ("UV", C.c_void_p)]
+
+
 EXPORTS = [
     # drop-in, vfgs_hw.h:51-62
     "vfgs_set_luma_pattern", "vfgs_set_chroma_pattern", "vfgs_set_scale_lut", "vfgs_set_pattern_lut",
@@ -176,7 +183,7 @@ EXPORTS = [
     "vfgs_hip_dev_build", "vfgs_hip_init_devices", "vfgs_hip_overlap_begin", "vfgs_hip_overlap_end", "vfgs_hip_get_stream_stats", "vfgs_hip_line_lookahead", "vfgs_hip_declare_frame",
     "vfgs_hip_get_stripe_stream_stats", "vfgs_hip_lfsr_segments",
     "vfgs_hip_add_grain_frame_list_seeded_dev", "vfgs_hip_add_grain_frame_list_seeded_part_dev", "vfgs_hip_add_grain_frame_list_seeded_copy_dev",
-    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
+    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
 ]
@@ -307,6 +314,25 @@ class VfgsHip:
         assert len(src) == len(dst) and (seeds is None or len(seeds) == len(src))
         self._ck(self.lib.vfgs_hip_add_grain_frame_list_seeded_copy8_dev(self.frame_list(src), self.frame_list(dst), self.seed_list(seeds), len(src),
                                                                          width, height, stride, cstride, dstride, dcstride, stream))
+
+    @staticmethod
+    def sp_frame_list(frames):
+        """frames: sequence of (Y, UV) device addresses -> ctypes array of vfgs_hip_sp_frame (like frame_list)."""
+        if isinstance(frames, C.Array):
+            return frames
+        arr = (SpFrame * len(frames))()
+        for k, (y, uv) in enumerate(frames):
+            arr[k].Y, arr[k].UV = y, uv
+        return arr
+
+    def add_grain_sp_frame_list_dev(self, src, dst, seeds, width, height, stride, uv_stride, sample_shift, stream=0):
+        """Semi-planar frames (NV12 / NV16 / P010 / P210 / P012): a luma plane and one plane of Cb/Cr pairs each; dst is src (or None): in
+        place; seeds None: one seed sequence, else a seed per picture; sample_shift 0 or 16 - depth (include/vfgs_hip.h)."""
+        s = self.sp_frame_list(src)
+        d = s if (dst is None or dst is src) else self.sp_frame_list(dst)
+        assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
+        self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
+                                                               sample_shift, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
