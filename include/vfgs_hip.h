@@ -254,11 +254,20 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
  * (vfgs_set_depth).  Bytes outside the whole blocks of a row and rows outside the picture are never written, in place or out of place.
  * One launch per 32 frames (vfgs_hip_last_launch_info().kernel: grain_sp_kernel<depth,csuby,oney,onec>); inside an overlap region the
  * call alternates over the two internal streams like every other device-pointer call.
+ * An active chroma mix (vfgs_hip_set_chroma_mix, or the firmware's AFGS1 programming of it) is HONOURED: the samples written and the seed
+ * registers are those of the planar copy list on D(src[f]) with the same mix active -- the luma that enters the mix is the source's,
+ * >> sample_shift like every source container, the last luma sample of a row pairs with itself -- for one-pattern models at depth 8 and
+ * 10 (kernel: grain_sp_mix_kernel<depth,csuby>; one read of the luma over a UV row serves Cb and Cr, a mix on one component only
+ * included).  Chroma reads the luma of BEFORE the call: where any destination luma plane of a launch shares bytes with any source luma
+ * plane of it (in place; also a destination Y that is the source Y with the UV plane elsewhere) the 32 frames are TWO launches on the
+ * stream, the UV rows first, then luma -- `launches` counts both; fully out of place they are one.
  * Refused before anything changes (a refused call does not reseed): everything the list calls above refuse, with the same codes -- a null
  * list or plane 18, a misaligned pointer 7, bad geometry, destination planes that share bytes 18 (a UV plane that overlaps another
  * frame's Y included), a source plane that shares bytes with another frame's destination 18 -- and, error 40 with a message that names
  * the cause: csubx != 2; sample_shift not in {0, 16 - depth}, or non-zero at depth 8; width > 8192 (rows walked in parts); an active
- * chroma mix (its kernels read planar chroma).  An empty list is no call at all.
+ * chroma mix ("chroma mix" in the message) with a programmed model that needs a general-form pattern bank, or at depth 12 -- the two
+ * cases the planar calls refuse with error 38 on D(src); like every device-pointer call this one runs on the primary device, also while
+ * several devices are set (vfgs_hip_init_devices), and honours the mix there.  An empty list is no call at all.
  * Out of scope, on purpose: stripe / part forms, the narrowed 8-bit destination, host-memory entry points, 4:4:4 semi-planar,
  * persistent luma workgroups. */
 typedef struct vfgs_hip_sp_frame { void* Y; void* UV; } vfgs_hip_sp_frame;

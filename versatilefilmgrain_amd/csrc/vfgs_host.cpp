@@ -1498,14 +1498,18 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	if (image_is_current(s, wide)) { form_one_y = s.img_one_y; form_one_c = s.img_one_c; }
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
+	// (the semi-planar call refuses the same cases under its own code, 40: the two entries stay congruent on the planar picture)
 	const bool mix = mix_active();
-	if (mix && sp) return fail(19, "internal: semi-planar frames with an active chroma mix");
+	const int mix_code = sp ? 40 : 38;
+	const char* const mix_who = sp ? "semi-planar frames: " : "";
 	if (mix && s.bs == 4)
-		return fail(38, "a chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit");
+		return fail(mix_code, "%sa chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit", mix_who);
 	if (mix && !(form_one_y && form_one_c))
-		return fail(38, "a chroma mix is active and the programmed model needs a general-form pattern bank (%s rows): not supported", wide ? "wide" : "ordinary");
+		return fail(mix_code, "%sa chroma mix is active and the programmed model needs a general-form pattern bank (%s rows): not supported", mix_who, wide ? "wide" : "ordinary");
+	// (only the host-memory entries run on another state; the semi-planar call, like every device-pointer call, is the primary device's)
 	if (mix && &s != &g_states[0])
-		return fail(38, "a chroma mix is active: not supported on the devices of vfgs_hip_init_devices");
+		return sp ? fail(19, "internal: semi-planar frames on a device of vfgs_hip_init_devices")
+		          : fail(38, "a chroma mix is active: not supported on the devices of vfgs_hip_init_devices");
 	for (int pass = 0; pass < 3; pass++)
 	{
 		long waves = 0;
@@ -1664,8 +1668,14 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	const bool in_region = g_states[0].ov.active && (stream == g_states[0].ov.s[0] || stream == g_states[0].ov.s[1]);
 	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + (sp ? 1 : 2) * cext) >= (64u << 20)) ? 1 : 0;
 #endif
+	if (sp)
+	{
+		a.sp_kernel = 1;
+		a.sp_shift2 = (uint32_t)sp_shift * 0x10001u;
+	}
 	if (mix)
 	{
+		// (semi-planar frames: grain_sp_mix_kernel, whose UV workgroups read the luma over their rows; the same two-launch rule)
 		if (!(s.img_one_y && s.img_one_c) || persist) return fail(19, "internal: the table image is not the form the chroma mix was admitted for");
 		a.mix_kernel = 1;
 		a.mix_lw = (int)width;
@@ -1693,11 +1703,6 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, true, true, wide, false, (int)grid, stream));
 			a.mix_planes = 2;      // luma only
 		}
-	}
-	if (sp)
-	{
-		a.sp_kernel = 1;
-		a.sp_shift2 = (uint32_t)sp_shift * 0x10001u;
 	}
 	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist, (int)grid, stream));
 	if (seeds) seeded_done();
@@ -1741,6 +1746,12 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			// (the kernels of semi-planar frames: depth, chroma subsampling y, one-pattern luma, one-pattern chroma; "chroma" in the per-plane figures is the UV plane)
 			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, s.img_one_c));
 			snprintf(li.kernel, sizeof li.kernel, "grain_sp_kernel<%d,%d,%s,%s>", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false", s.img_one_c ? "true" : "false");
+			if (mix)
+			{
+				// (... under the mix: depth, chroma subsampling y; all-one-pattern images)
+				li.lds_bytes_per_workgroup = vfgs::sp_mix_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, true));
+				snprintf(li.kernel, sizeof li.kernel, "grain_sp_mix_kernel<%d,%d>", 8 + s.bs, s.csuby);
+			}
 		}
 		g_last_launch_valid = true;
 	}
@@ -3072,8 +3083,10 @@ int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfg
 		return fail(40, "semi-planar frames: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
 	if (width > (unsigned)vfgs::kTileBlocks * 16)
 		return fail(40, "semi-planar frames: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
-	if (mix_active())
-		return fail(40, "semi-planar frames: a chroma mix is active (the kernels of the mix read planar chroma)");
+	// (an active mix is honoured for all-one-pattern models at 8 and 10 bit; a general-form model under a mix is refused in run_device, where
+	// the form of the table image is known, with this code and before any state moves)
+	if (mix_active() && s.bs == 4)
+		return fail(40, "semi-planar frames: a chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit");
 	if (!src || !dst) return fail(18, "frame list: null list");
 	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd;
 	for (unsigned f = 0; f < nframes; f++) ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};

@@ -1288,7 +1288,14 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 //     ONE load of the block row's LFSR words: Cb and Cr take different bit fields of the same register (block_param);
 //   * row ends are the buffer descriptor's range check, per dword: an 8-bit row of an odd number of blocks ends in half a 32-byte unit;
 //   * rows are at most kTileBlocks blocks (the host refuses wider pictures): one parameter table per component and block row.
-template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG>
+//
+// MIX (UV workgroups of grain_sp_mix_kernel; DESIGN.md 4.7 "the mix on semi-planar frames"): a position also loads the 32 bytes of luma row
+// cy * SUBY that lie over a lane's 32-byte UV unit -- at either container size the luma over a UV unit begins at the UV unit's own byte offset
+// of its row -- as two 16-byte buffer loads through a descriptor of the LUMA row (range-checked against what that row has left), plain loads
+// issued with the position's own: they are part of the ring.  ONE read of the luma serves both components: mix_index runs on the split Cb
+// unit and on the split Cr unit with the same luma registers, each with its component's multipliers; the index dwords take the samples' lane
+// shift and carry, and grain_unit's LUT gathers read them.
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
@@ -1301,7 +1308,8 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int RPB = 16 / SUBY;
 	constexpr int K = M::SHIFT * SZ / 4;                 // dwords of a planar unit that belong to the lane before its own
 	constexpr int BPS = 64 * M::BPL;                     // grain blocks a position advances by
-	constexpr int NU = kSpRing;
+	constexpr int NU = MIX ? kSpMixRing : kSpRing;
+	static_assert(!MIX || ONE, "the mix exists for one-pattern chroma");
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
 	constexpr int IMG = sp_uv_image_bytes(CIMG, LUTB, ONE);
@@ -1376,10 +1384,28 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 		w[u][0] = lo.x; w[u][1] = lo.y; w[u][2] = lo.z; w[u][3] = lo.w;
 		w[u][4] = hi.x; w[u][5] = hi.y; w[u][6] = hi.z; w[u][7] = hi.w;
 	};
+	// MIX: the luma over my UV units (row cy * SUBY of the frame's luma plane, the same byte offset in its row), in the ring with them
+	const PlaneDesc& pl = a.pd[0];
+	const uint8_t* lbase = MIX ? ft.src[0][f] : nullptr;
+	auto lrow_off = [&](int k) { return (uint32_t)((base + RSTR * k) * SUBY * (int)pl.pitch); };     // (whole frames: the plane pointer addresses line 0)
+	// (a luma row of whole blocks has the bytes of a UV row of whole blocks -- launch_depth refuses anything else -- so left() is what it has left too)
+	uint32_t lw[MIX ? NU : 1][8];
+	auto load_luma = [&](const __amdgpu_buffer_rsrc_t rs, const int u) {
+		const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB, 0, 0);
+		const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB + 16, 0, 0);
+		lw[u][0] = lo.x; lw[u][1] = lo.y; lw[u][2] = lo.z; lw[u][3] = lo.w;
+		lw[u][4] = hi.x; lw[u][5] = hi.y; lw[u][6] = hi.z; lw[u][7] = hi.w;
+	};
 	{
 		const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(sbase + (k0 < k1 ? row_off(k0) : 0u), k0 < k1 ? left(0) : 0u);
 #pragma unroll
 		for (int u = 0; u < NU; u++) load_pos(rs0, u);
+		if constexpr (MIX)
+		{
+			const __amdgpu_buffer_rsrc_t ls0 = make_rsrc(lbase + (k0 < k1 ? lrow_off(k0) : 0u), k0 < k1 ? left(0) : 0u);
+#pragma unroll
+			for (int u = 0; u < NU; u++) load_luma(ls0, u);
+		}
 	}
 #pragma unroll
 	for (int it = 0; it < NIT; it++)
@@ -1428,10 +1454,18 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	uint32_t carry[2][K];                  // in lane 0: the last K dwords of lane 63 of the previous position of the row, per component
 	uint32_t outp[2][4] = {};              // the previous position's planar units: dwords K.. of its lanes
 	uint32_t tp[2][K] = {};                // ... and the first K dwords its lanes computed: they belong one lane down
+	uint32_t mcarry[2][K];                 // MIX: the carry of the index dwords
 #pragma unroll
 	for (int c = 0; c < 2; c++)
 #pragma unroll
-		for (int d = 0; d < K; d++) carry[c][d] = 0;
+		for (int d = 0; d < K; d++) carry[c][d] = mcarry[c][d] = 0;
+	// MIX: per component { luma_mult, chroma_mult, offset, active } (a component without a mix of its own keeps the sample as its index)
+	// (each value a scalar register of its own: the eight come out of ONE scalar load, and kept as its 8-register tuple they would be spilled as
+	// one -- to a stack slot, the only scratch of the kernel; grain_sp_mix_kernel below says what guards this and what to do when it stops working)
+	auto own = [](int v) { if constexpr (MIX) asm("" : "+s"(v)); return v; };
+	const int mix_lm[2] = {MIX ? own(a.mix[0][0]) : 0, MIX ? own(a.mix[1][0]) : 0}, mix_cm[2] = {MIX ? own(a.mix[0][1]) : 0, MIX ? own(a.mix[1][1]) : 0};
+	const int mix_off[2] = {MIX ? own(a.mix[0][2]) : 0, MIX ? own(a.mix[1][2]) : 0};
+	const bool mix_on[2] = {MIX && own(a.mix[0][3]) != 0, MIX && own(a.mix[1][3]) != 0};
 	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);
 	// the previous position is complete: interleave its two planar units, shift them up, store 32 bytes
 	auto store_prev = [&](const __amdgpu_buffer_rsrc_t rs, const uint32_t off) {
@@ -1458,6 +1492,16 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 		const uint32_t rowoff = (uint32_t)j * RS, uprowoff = (uint32_t)(RPB + j) * RS;
 		const int wc_ = jrow == 0 ? (SUBY > 1 ? 20 : 12) : 24, wu_ = jrow == 0 ? (SUBY > 1 ? 20 : 24) : 12;
 		const uint32_t ro = row_off(k);
+		// MIX: the row's last luma sample, low-aligned: the partner of every pair behind it (the lanes at the row's end only)
+		uint32_t lw1 = 0;
+		const uint32_t lro = MIX ? lrow_off(k) : 0u;
+		if constexpr (MIX)
+		{
+			const __amdgpu_buffer_rsrc_t lrs = make_rsrc(lbase + lro, pl.rowbytes);
+			const uint32_t at = (uint32_t)(a.mix_lw - 1) * SZ;
+			if constexpr (SZ == 2) lw1 = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(lrs, at, 0, 0) >> (a.sp_shift2 & 0xffffu);
+			else lw1 = (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(lrs, at, 0, 0);
+		}
 		for (int g = 0; g < ngroups; g++)
 		{
 			const bool lastg = g + 1 == ngroups;
@@ -1465,6 +1509,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 			const bool nvalid = !lastg || k + 1 < k1;
 			const uint32_t nso = nvalid ? (lastg ? row_off(k + 1) : ro) + (uint32_t)ng * GB : 0u;
 			const __amdgpu_buffer_rsrc_t nsrc = make_rsrc(sbase + nso, nvalid ? left(ng) : 0u);
+			const __amdgpu_buffer_rsrc_t nlsrc = make_rsrc(lbase + (MIX && nvalid ? (lastg ? lrow_off(k + 1) : lro) + (uint32_t)ng * GB : 0u), MIX && nvalid ? left(ng) : 0u);
 			const __amdgpu_buffer_rsrc_t cdst = make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
 			const uint8_t* pe = lds + idx0 + (uint32_t)(g * NU * BPS * 4);
 			const int clg = cl + g * NU * BPS;
@@ -1487,8 +1532,29 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 #pragma unroll
 						for (int q = 0; q < 4; q++) cw[c][q] = pk_lshr_b16(a.sp_shift2, cw[c][q]);
 				}
+				// MIX: the index dwords of my two planar units from ONE copy of the luma over them
+				uint32_t mi[2][4] = {};
+				if constexpr (MIX)
+				{
+					uint32_t l[8];
+#pragma unroll
+					for (int q = 0; q < 8; q++) l[q] = DEPTH > 8 ? pk_lshr_b16(a.sp_shift2, lw[u][q]) : lw[u][q];
+					const int nv = a.mix_lw - 1 - (((NU * g + u) * 64 + lane) * NS * 2);
+#pragma unroll
+					for (int c = 0; c < 2; c++)
+					{
+						if (mix_on[c])
+							mix_index<DEPTH, 2>(cw[c], l, mix_lm[c], mix_cm[c], mix_off[c], nv, lw1, mi[c]);
+						else
+						{
+#pragma unroll
+							for (int d = 0; d < 4; d++) mi[c][d] = cw[c][d];
+						}
+					}
+				}
 				// the registers are free: refill them with the position NU steps ahead
 				load_pos(nsrc, u);
+				if constexpr (MIX) load_luma(nlsrc, u);
 				const bool live = NU * g + u < tsegs;
 				bool edge_on[NE];
 #pragma unroll
@@ -1507,6 +1573,17 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 					for (int d = 0; d < K; d++) carry[c][d] = rot_up(cw[c][4 - K + d]);
 #pragma unroll
 					for (int d = K; d < 4; d++) t[d] = cw[c][d - K];
+					// (the index dwords: the same lane shift and carry as the samples)
+					uint32_t ti[4] = {};
+					if constexpr (MIX)
+					{
+#pragma unroll
+						for (int d = 0; d < K; d++) ti[d] = lane_up(firsts ? 0u : mcarry[c][d], mi[c][4 - K + d]);
+#pragma unroll
+						for (int d = 0; d < K; d++) mcarry[c][d] = rot_up(mi[c][4 - K + d]);
+#pragma unroll
+						for (int d = K; d < 4; d++) ti[d] = mi[c][d - K];
+					}
 					if (live)
 					{
 						RunParam<NR> rp, up;
@@ -1514,7 +1591,10 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 						for (int rr = 0; rr < NR; rr++) rp.pa[rr] = *(const uint32_t*)(pe + PT + (2 * c) * kParamTableBytes + (u * BPS + rr) * 4);
 #pragma unroll
 						for (int rr = 0; rr < NR; rr++) up.pa[rr] = OV ? *(const uint32_t*)(pe + PT + (2 * c + 1) * kParamTableBytes + (u * BPS + rr) * 4) : 0u;
-						grain_unit<DEPTH, BW, OV, ONE, ONE, NEG>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, t);
+						if constexpr (MIX)
+							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG, true>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, ti);
+						else
+							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, t);
 					}
 #pragma unroll
 					for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(rot_down(t[d]), tp[c][d]);
@@ -1567,6 +1647,42 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp_kernel(
 		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
 		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
+}
+
+// The kernels of semi-planar frames under the luma / chroma mix (KernelArgs::sp_kernel AND mix_kernel): all-one-pattern images
+// only, depths 8 and 10, the grid and the workgroup numbering of grain_sp_kernel.  Luma workgroups are grain_sp_kernel's; a UV workgroup holds
+// the luma over its units in its ring and forms both components' index dwords from it.  KernelArgs::mix_planes switches the workgroups of one
+// plane type off, as in grain_mix_kernel: a call whose destination luma shares bytes with its source luma is two launches on its stream, UV
+// first.  kSpMixWgPerCU workgroups per CU: launch bounds and LDS allocation say the same (vfgs_layout.h).
+template <int DEPTH, int CSUBY>
+__global__ __launch_bounds__(kWavesPerWG * 64, kSpMixWgPerCU) void grain_sp_mix_kernel(const KernelArgs a, const FrameTable ft)
+{
+	constexpr ImageLayout L = image_layout(2, CSUBY, true, true, DEPTH == 8);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[sp_mix_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, true))];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	const int r = (int)(blockIdx.x >> a.lfronts);
+	const bool luma = r < a.pd[0].wgs;
+	if (f >= a.nframes || (a.mix_planes & (luma ? 1 : 2))) return;
+	// (these eight arguments arrive with ONE scalar load and both walks read them: each in a scalar register of its own from here on.  Kept as
+	// the load's 8-register tuple across the UV walk, the register allocator gives the tuple a stack slot and then reloads it from the
+	// arguments instead -- the slot stays in the kernel's frame, unused, and every dispatch would get scratch memory for it)
+	// This steers the register allocator, it forces nothing, and it depends on the compiler: its ONLY guard is tests/test_code_object_sp_mix_cpu.py
+	// (private_segment_fixed_size == 0).  If a new ROCm makes that test fail: compile with -Rpass-analysis=stack-frame-layout, which names the
+	// size of the slot ("Type: Spill, Size: 32" is an 8-register tuple, 16 a 4-register one); find the scalar load of that width that is issued
+	// twice from the same argument offset in the kernel's assembly (`b` below is a copy in registers, never in memory: it costs nothing); add the
+	// fields at that offset to the list below -- or, if that no longer helps, lower the scalar pressure of the UV walk.  Never accept the scratch.
+	KernelArgs b = a;
+	auto own = [](auto& v) { asm("" : "+s"(v)); };
+	own(b.cur_bit0); own(b.up_bit0); own(b.frame_bit_step); own(b.y0); own(b.nblk); own(b.nbrows); own(b.nframes); own(b.listed);
+	// (the same for the four of the luma geometry that arrive with pd[0].wgs above)
+	own(b.pd[0].nrows); own(b.pd[0].wgs); own(b.pd[0].rw_segs); own(b.pd[0].rw_rpw);
+	if (luma)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, true, L.y_neg, 0, false, false, false, false, true>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, true, L.c_neg, true>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1647,14 +1763,33 @@ static hipError_t launch_sp(const KernelArgs& a, const FrameTable& ft, bool oney
 	return hipGetLastError();
 }
 
+template <int DEPTH, int CSUBY>
+static hipError_t launch_sp_mix(const KernelArgs& a, const FrameTable& ft, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	hipLaunchKernelGGL((grain_sp_mix_kernel<DEPTH, CSUBY>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
 template <int D>
 static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
 {
 	if (a.sp_kernel)
 	{
-		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table, no mix (the host refuses everything else)
-		if (a.mix_kernel || out8 || wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
+		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table (the host refuses everything else)
+		if (out8 || wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
 		if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
+		if (a.mix_kernel)
+		{
+			// (the mix: all-one-pattern images at 8 and 10 bit; launch_depth<12> instantiates none, the host refuses such a call before it gets here)
+			if (!oney || !onec || a.pd[0].rowbytes != a.pd[1].rowbytes) return hipErrorInvalidValue;
+			if constexpr (D != 12)
+			{
+				if (csuby == 2) return launch_sp_mix<D, 2>(a, ft, grid, stream);
+				if (csuby == 1) return launch_sp_mix<D, 1>(a, ft, grid, stream);
+			}
+			return hipErrorInvalidValue;
+		}
 		if (csuby == 2) return launch_sp<D, 2>(a, ft, oney, onec, grid, stream);
 		if (csuby == 1) return launch_sp<D, 1>(a, ft, oney, onec, grid, stream);
 		return hipErrorInvalidValue;

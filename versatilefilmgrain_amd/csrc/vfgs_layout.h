@@ -138,6 +138,18 @@ constexpr int sp_lds_allocation(const int need)
 	return need > target ? need : target;
 }
 
+// The kernels of semi-planar frames under the luma / chroma mix (grain_sp_mix_kernel): a UV wave keeps, per ring position, its 32 bytes of UV
+// AND the 32 bytes of luma over them, and per component the index dwords and their carries beside the samples': more than the 128 registers of
+// four workgroups per CU.  THREE workgroups per CU (three waves per SIMD: 168 registers), by launch bounds and by an LDS allocation that says
+// the same; the ring keeps the two positions of grain_sp_kernel.
+constexpr int kSpMixRing = 2;
+constexpr int kSpMixWgPerCU = 3;
+constexpr int sp_mix_lds_allocation(const int need)
+{
+	const int target = (kLdsPerCU / kSpMixWgPerCU) & ~2047;
+	return need > target ? need : target;
+}
+
 // Device image of everything the kernel looks up: one sub-image per plane type (luma; chroma) -- or per chroma
 // component -- and a workgroup (which works on ONE plane) copies the sub-image of its plane to LDS offset 0.
 //

@@ -327,7 +327,10 @@ class VfgsHip:
 
     def add_grain_sp_frame_list_dev(self, src, dst, seeds, width, height, stride, uv_stride, sample_shift, stream=0):
         """Semi-planar frames (NV12 / NV16 / P010 / P210 / P012): a luma plane and one plane of Cb/Cr pairs each; dst is src (or None): in
-        place; seeds None: one seed sequence, else a seed per picture; sample_shift 0 or 16 - depth (include/vfgs_hip.h)."""
+        place; seeds None: one seed sequence, else a seed per picture; sample_shift 0 or 16 - depth (include/vfgs_hip.h).  An active chroma mix
+        (set_chroma_mix, or the firmware's AFGS1 programming) is honoured for one-pattern models at depth 8 and 10: the result is the planar
+        copy list's on the de-interleaved picture under the same mix; where a destination Y shares bytes with a source Y the call is two
+        launches (UV rows first).  A general-form model or depth 12 under a mix: VfgsHipError 40, nothing changed."""
         s = self.sp_frame_list(src)
         d = s if (dst is None or dst is src) else self.sp_frame_list(dst)
         assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
