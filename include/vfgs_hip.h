@@ -268,8 +268,8 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
  * chroma mix ("chroma mix" in the message) with a programmed model that needs a general-form pattern bank, or at depth 12 -- the two
  * cases the planar calls refuse with error 38 on D(src); like every device-pointer call this one runs on the primary device, also while
  * several devices are set (vfgs_hip_init_devices), and honours the mix there.  An empty list is no call at all.
- * Out of scope, on purpose: stripe / part forms, the narrowed 8-bit destination, host-memory entry points, 4:4:4 semi-planar,
- * persistent luma workgroups. */
+ * Out of scope, on purpose: stripe / part forms, host-memory entry points, 4:4:4 semi-planar, persistent luma workgroups (the narrowed
+ * 8-bit destination is the _copy8 call below). */
 typedef struct vfgs_hip_sp_frame { void* Y; void* UV; } vfgs_hip_sp_frame;
 int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                          const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
@@ -277,6 +277,35 @@ int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfg
                                          unsigned stride, unsigned uv_stride,   /* in samples (container elements) of a Y row / a UV row */
                                          unsigned sample_shift,      /* 0, or 16 - depth: samples sit in the high bits (P010: 6, P012: 4) */
                                          void* stream);
+
+/* ... with the NARROWED 8-BIT DESTINATION: P010 / P210 / P012 in, NV12 / NV16 out, what a player does that decodes to 10 or 12 bit and
+ * displays or encodes 8 bit (the reference CLI's --outdepth 8, yuv_to_8bit, yuv.c:216-258, folded into the store like the planar _copy8
+ * calls: the clean picture stays a reference frame, the grained copy leaves at half the write traffic).
+ *   src[f]       a semi-planar picture at the programmed depth (10 or 12) in uint16 containers, exactly as above; stride, uv_stride in
+ *                containers, sample_shift 0 or 16 - depth;
+ *   dst[f]       a semi-planar picture of uint8 containers, no shift: NV12 at 4:2:0, NV16 at 4:2:2; dst_stride, dst_uv_stride in BYTES,
+ *                each >= 16 * ceil(width / 16) and a multiple of 16; pointers 16-byte aligned;
+ *   seeds        NULL: one seed sequence; else a seed per picture.
+ * With D(p) as above, the bytes written are those vfgs_hip_add_grain_frame_list_copy8_dev (with seeds: _seeded_copy8_dev) writes for
+ * D(src[f]), Cb and Cr interleaved again: a byte is (uint8)((v + 2) >> 2) of the grained, clipped sample v at depth 10,
+ * (uint8)((v + 8) >> 4) at depth 12; the four seed registers afterwards are that call's.  The low bits of a source container are ignored;
+ * with sample_shift == 0 a container above the depth's range wraps as in the planar calls.  Bytes outside the whole 16-sample blocks of
+ * the picture's rows (16 bytes of a Y row, 16 bytes = 8 Cb/Cr pairs of a UV row, per block) and rows outside the picture are never
+ * written.  One launch per 32 frames (vfgs_hip_last_launch_info(): out8 = 1, kernel grain_sp8_kernel<depth,csuby,oney,onec>); inside an
+ * overlap region the call alternates over the two internal streams like every other device-pointer call.
+ * Refused before anything changes (a refused call does not reseed): everything the call above refuses, with the same codes (40: csubx != 2,
+ * a bad sample_shift, width > 8192; 18, 7, 6, 5 as there); depth 8: error 16, as in the planar _copy8 calls; dst_stride or dst_uv_stride
+ * too small: 6, not a multiple of 16: 8, as in the planar _copy8 list; a destination plane that shares bytes with another destination
+ * plane or with ANY source plane of the call, its own frame's included: 18 -- the containers differ in size, there is no in-place form;
+ * an active chroma mix: 40, "chroma mix" in the message (the kernels of the mix have no narrowed semi-planar form).
+ * Out of scope, on purpose: the mix with a narrowed destination, stripe / part forms, host-memory entry points, 4:4:4, widths above 8192. */
+int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
+                                               const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
+                                               unsigned nframes, unsigned width, unsigned height,
+                                               unsigned stride, unsigned uv_stride,          /* source, in 16-bit containers */
+                                               unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
+                                               unsigned sample_shift,      /* 0, or 16 - depth */
+                                               void* stream);
 
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).

@@ -1449,6 +1449,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	if (list && nframes > (unsigned)vfgs::kListFrames) return fail(19, "internal: a listed launch holds at most %d frames", vfgs::kListFrames);
 	if (int e = ensure_init(-1)) return e;
 	if (int e = check_geometry(s, sY, sU, sV, width, stride, cstride)) return e;
+	const bool sp = sp_shift >= 0;
 	if (!dg.out8)
 	{
 		if (int e = check_geometry(s, dY, dU, dV, width, stride, cstride)) return e;
@@ -1457,13 +1458,13 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	{
 		const unsigned nb = (width + 15) / 16;
 		if (s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
-		if (dg.stride < nb * 16 || dg.cstride < nb * 16 / s.csubx) return fail(6, "destination stride too small");
+		// (semi-planar frames: a UV row of bytes holds Cb AND Cr of its blocks, as many bytes as the luma row)
+		if (dg.stride < nb * 16 || dg.cstride < (sp ? nb * 16 : nb * 16 / s.csubx)) return fail(6, "destination stride too small");
 		if ((((uintptr_t)dY | (uintptr_t)dU | (uintptr_t)dV) & 15) || dg.stride % 16 || dg.cstride % 16 || (dg.ypitch | dg.cpitch) % 16)
 			return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
 	}
 	if (seeds && (frame_y != 0 || !list)) return fail(19, "internal: seeds belong to lists of frames that begin at line 0");
-	const bool sp = sp_shift >= 0;
-	if (sp && (!list || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
+	if (sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) return 0;
@@ -1524,7 +1525,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			d.dfpitch = dg.out8 ? (pt ? dg.cpitch : dg.ypitch) : d.fpitch;
 			// (semi-planar frames: "chroma" is the one plane of interleaved Cb/Cr pairs, a row of whole blocks as many containers as a luma row)
 			d.rowbytes = nblk * bw * sz * ((sp && pt) ? 2 : 1);
-			d.drowbytes = dg.out8 ? nblk * bw : d.rowbytes;
+			d.drowbytes = dg.out8 ? nblk * bw * ((sp && pt) ? 2 : 1) : d.rowbytes;
 			d.nrows = pt ? (int)((part_y + part_h + suby - 1) / suby) - (int)((part_y + suby - 1) / suby) : (int)part_h;
 			auto lg = [](int v) { int l = 0; while ((1 << l) < v) l++; return l; };
 			const int ub = (sp && pt) ? vfgs::kSpUnitBytes : 16;   // (a lane's unit of an interleaved row: 32 bytes, vfgs_kernel.hip "UV walk")
@@ -1745,7 +1746,9 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		{
 			// (the kernels of semi-planar frames: depth, chroma subsampling y, one-pattern luma, one-pattern chroma; "chroma" in the per-plane figures is the UV plane)
 			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, s.img_one_c));
-			snprintf(li.kernel, sizeof li.kernel, "grain_sp_kernel<%d,%d,%s,%s>", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false", s.img_one_c ? "true" : "false");
+			// (grain_sp8_kernel: the same family with the narrowed 8-bit destination)
+			snprintf(li.kernel, sizeof li.kernel, "%s<%d,%d,%s,%s>", dg.out8 ? "grain_sp8_kernel" : "grain_sp_kernel", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false",
+			         s.img_one_c ? "true" : "false");
 			if (mix)
 			{
 				// (... under the mix: depth, chroma subsampling y; all-one-pattern images)
@@ -2935,6 +2938,8 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 	// a race where consecutive calls are not, and so would a source plane of one frame that shares bytes with the destination of
 	// ANOTHER (that frame may already have been grained when it is read).  The bytes of a plane: its rows of the stripe, whole
 	// 16-sample blocks each (check_geometry).  A frame's own source and destination are either the same plane (in place) or disjoint.
+	// (semi-planar frames with the narrowed destination: containers of another size, so there is no in-place form -- disjoint, always)
+	const bool no_in_place = sp && dg.out8;
 	{
 		const uint64_t sz = s.bs ? 2 : 1, nblk = (width + 15) / 16;
 		const uint64_t crows = part_h ? (uint64_t)(part_y + part_h - 1) / s.csuby - part_y / s.csuby + 1 : 0;
@@ -2966,7 +2971,7 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 				// destinations are disjoint and sorted: the first one that ends behind lo is the only candidate below hi ... and its successors
 				auto it = std::upper_bound(d.begin(), d.end(), lo, [](uintptr_t v, const Span& x) { return v < x.hi; });
 				for (; it != d.end() && it->lo < hi; ++it)
-					if (!(it->frame == f && pl[c] == own[c] && it->lo == lo))
+					if (no_in_place || !(it->frame == f && pl[c] == own[c] && it->lo == lo))
 						return fail(18, "frame list: a source plane of frame %u shares bytes with a destination plane of frame %u", f, it->frame);
 			}
 		}
@@ -3097,6 +3102,44 @@ int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfg
 	}
 	return run_frame_list(ps.data(), src != dst ? pd.data() : ps.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), DstGeom(), true, 0, 0,
 	                      seeds != nullptr, seeds, (int)sample_shift);
+}
+
+// ... with the narrowed 8-bit destination (P010 / P210 / P012 in, NV12 / NV16 out): the call above with a destination geometry of its own.
+// Nothing is in place here; the mix has no narrowed semi-planar kernel.
+int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
+                                               unsigned width, unsigned height, unsigned stride, unsigned uv_stride, unsigned dst_stride,
+                                               unsigned dst_uv_stride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	if (s.csubx != 2)
+		return fail(40, "semi-planar frames: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
+	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
+		return fail(40, "semi-planar frames: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
+	if (width > (unsigned)vfgs::kTileBlocks * 16)
+		return fail(40, "semi-planar frames: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
+	if (s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
+	if (mix_active())
+		return fail(40, "semi-planar frames: a chroma mix is active and the destination is narrowed to 8 bit: the kernels of the mix have no such form");
+	if (!src || !dst) return fail(18, "frame list: null list");
+	// (the destination's pitches, with the codes of the planar _copy8 list: a UV row of bytes is as long as the luma row)
+	const unsigned nb16 = (width + 15) / 16 * 16;
+	if (dst_stride < nb16 || dst_uv_stride < nb16) return fail(6, "destination stride too small");
+	if (dst_stride % 16 || dst_uv_stride % 16) return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
+	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd(nframes);
+	for (unsigned f = 0; f < nframes; f++)
+	{
+		ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};
+		pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
+	}
+	DstGeom dg;
+	dg.out8 = true;
+	dg.stride = dst_stride; dg.cstride = dst_uv_stride;
+	return run_frame_list(ps.data(), pd.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), dg, true, 0, 0, seeds != nullptr, seeds,
+	                      (int)sample_shift);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,

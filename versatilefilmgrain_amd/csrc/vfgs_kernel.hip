@@ -29,7 +29,8 @@
 //     pointers are a table IN the kernel arguments (FrameTable, vfgs_layout.h) and a workgroup reads its frame's with scalar loads;
 //   * semi-planar frames (a luma plane + ONE plane of interleaved Cb/Cr pairs, samples possibly in the high bits of their containers) have a
 //     kernel family of their own, grain_sp_kernel: the luma walk with a container shift, and a UV walk whose lanes move 32 bytes and split
-//     them into one planar Cb unit and one planar Cr unit ("UV walk" below).
+//     them into one planar Cb unit and one planar Cr unit ("UV walk" below); with the narrowed 8-bit destination (P010 in, NV12 out): grain_sp8_kernel,
+//     the same two walks with OUT8 -- a UV lane stores ONE 16-byte unit of Cb/Cr byte pairs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -676,6 +677,7 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     the unit's layout (mix_index) and sends them through the same lane shift as the samples.
 //   * SP (luma planes of grain_sp_kernel, 16-bit containers): the samples sit KernelArgs::sp_shift2 bits up in their containers; a position's
 //     units are shifted down as they leave the ring and the results up before they go to memory (a packed 16-bit shift per dword each way).
+//     SP with OUT8 (luma planes of grain_sp8_kernel): shifted down the same way, then narrowed like any OUT8 plane and not shifted up.
 template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, bool SP = false>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
@@ -703,7 +705,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(IMG_BYTES % 16 == 0, "table image in whole 16-byte units");
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
-	static_assert(!SP || (NARROW == 0 && !OUT8 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk");
+	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
@@ -1102,7 +1104,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				}
 				uint32_t o[DW];
 				results(t, o);
-				if constexpr (SP && DEPTH > 8)
+				if constexpr (SP && DEPTH > 8 && !OUT8)     // (the narrowed destination holds plain bytes)
 				{
 #pragma unroll
 					for (int d = 0; d < DW; d++) o[d] = pk_lshl_b16(a.sp_shift2, o[d]);
@@ -1295,7 +1297,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // issued with the position's own: they are part of the ring.  ONE read of the luma serves both components: mix_index runs on the split Cb
 // unit and on the split Cr unit with the same luma registers, each with its component's multipliers; the index dwords take the samples' lane
 // shift and carry, and grain_unit's LUT gathers read them.
-template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false>
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
@@ -1310,6 +1312,9 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int BPS = 64 * M::BPL;                     // grain blocks a position advances by
 	constexpr int NU = MIX ? kSpMixRing : kSpRing;
 	static_assert(!MIX || ONE, "the mix exists for one-pattern chroma");
+	constexpr int DW = OUT8 ? 2 : 4;                     // dwords of a component's planar unit in the destination ...
+	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of them belong to the lane before its own
+	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0 && !MIX), "the narrowed destination exists for 16-bit containers, without the mix");
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
 	constexpr int IMG = sp_uv_image_bytes(CIMG, LUTB, ONE);
@@ -1377,6 +1382,11 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr uint32_t GB = NU * UB;                     // ... of a group
 	auto row_off = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.pitch); };
 	auto left = [&](int g) { const uint32_t o = (uint32_t)g * GB; return o < pd.rowbytes ? min(pd.rowbytes - o, GB) : 0u; };
+	// (only the narrowed destination has a geometry of its own -- run_plane_rw: a lane's two 8-byte planar halves interleave into ONE 16-byte unit of
+	// Cb/Cr byte pairs, a wave access is 1 KiB)
+	constexpr uint32_t UBD = OUT8 ? kMaxUnits * 16 : UB, GBD = NU * UBD;
+	auto row_offd = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.dpitch); };
+	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD; return o < pd.drowbytes ? min(pd.drowbytes - o, GBD) : 0u; };
 	uint32_t w[NU][8];
 	auto load_pos = [&](const __amdgpu_buffer_rsrc_t rs, const int u) {
 		const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB, 0, LDA);
@@ -1452,8 +1462,8 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 
 	// ---- the walk ----------------------------------------------------------------------------------------------------
 	uint32_t carry[2][K];                  // in lane 0: the last K dwords of lane 63 of the previous position of the row, per component
-	uint32_t outp[2][4] = {};              // the previous position's planar units: dwords K.. of its lanes
-	uint32_t tp[2][K] = {};                // ... and the first K dwords its lanes computed: they belong one lane down
+	uint32_t outp[2][DW] = {};             // the previous position's planar units: dwords KD.. of its lanes' results
+	uint32_t tp[2][KD] = {};               // ... and the first KD dwords its lanes computed: they belong one lane down
 	uint32_t mcarry[2][K];                 // MIX: the carry of the index dwords
 #pragma unroll
 	for (int c = 0; c < 2; c++)
@@ -1469,21 +1479,44 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);
 	// the previous position is complete: interleave its two planar units, shift them up, store 32 bytes
 	auto store_prev = [&](const __amdgpu_buffer_rsrc_t rs, const uint32_t off) {
-		uint32_t st[8];
-#pragma unroll
-		for (int j = 0; j < 4; j++)
+		if constexpr (OUT8)
 		{
-			st[2 * j] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], JOIN_LO);
-			st[2 * j + 1] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], JOIN_HI);
-		}
-		if constexpr (DEPTH > 8)
-		{
+			// (bytes: Cb0 Cr0 Cb1 Cr1 | Cb2 Cr2 Cb3 Cr3 out of one dword of each component; 16 bytes = the lane's eight pairs, one vector store)
+			uint32_t s8[4];
 #pragma unroll
-			for (int j = 0; j < 8; j++) st[j] = pk_lshl_b16(a.sp_shift2, st[j]);
+			for (int j = 0; j < 2; j++)
+			{
+				s8[2 * j] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], 0x05010400u);
+				s8[2 * j + 1] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], 0x07030602u);
+			}
+			store_unit<4, STA>(rs, (uint32_t)lane * 16 + off, s8);
 		}
-		const uint32_t s0[4] = {st[0], st[1], st[2], st[3]}, s1[4] = {st[4], st[5], st[6], st[7]};
-		store_unit<4, STA>(rs, lane32 + off, s0);
-		store_unit<4, STA>(rs, lane32 + off + 16, s1);
+		else
+		{
+			uint32_t st[8];
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+			{
+				st[2 * j] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], JOIN_LO);
+				st[2 * j + 1] = __builtin_amdgcn_perm(outp[1][j], outp[0][j], JOIN_HI);
+			}
+			if constexpr (DEPTH > 8)
+			{
+#pragma unroll
+				for (int j = 0; j < 8; j++) st[j] = pk_lshl_b16(a.sp_shift2, st[j]);
+			}
+			const uint32_t s0[4] = {st[0], st[1], st[2], st[3]}, s1[4] = {st[4], st[5], st[6], st[7]};
+			store_unit<4, STA>(rs, lane32 + off, s0);
+			store_unit<4, STA>(rs, lane32 + off + 16, s1);
+		}
+	};
+	// OUT8: a component's results narrowed to 8 bit with the depth's rounding, four dwords -> two (run_plane_rw `results`)
+	auto narrow = [](const uint32_t (&t)[4], uint32_t (&o)[2]) {
+		uint32_t n[4];
+#pragma unroll
+		for (int d = 0; d < 4; d++) n[d] = ((t[d] + (0x00010001u << (DEPTH > 8 ? DEPTH - 9 : 0))) >> (DEPTH > 8 ? DEPTH - 8 : 0)) & 0x00ff00ffu;
+		o[0] = __builtin_amdgcn_perm(n[1], n[0], 0x06040200);
+		o[1] = __builtin_amdgcn_perm(n[3], n[2], 0x06040200);
 	};
 	auto walk_row = [&](auto overlap, const int k) {
 		constexpr bool OV = decltype(overlap)::value;
@@ -1510,7 +1543,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 			const uint32_t nso = nvalid ? (lastg ? row_off(k + 1) : ro) + (uint32_t)ng * GB : 0u;
 			const __amdgpu_buffer_rsrc_t nsrc = make_rsrc(sbase + nso, nvalid ? left(ng) : 0u);
 			const __amdgpu_buffer_rsrc_t nlsrc = make_rsrc(lbase + (MIX && nvalid ? (lastg ? lrow_off(k + 1) : lro) + (uint32_t)ng * GB : 0u), MIX && nvalid ? left(ng) : 0u);
-			const __amdgpu_buffer_rsrc_t cdst = make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
+			const __amdgpu_buffer_rsrc_t cdst = OUT8 ? make_rsrc(dbase + (row_offd(k) + (uint32_t)g * GBD), leftd(g)) : make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
 			const uint8_t* pe = lds + idx0 + (uint32_t)(g * NU * BPS * 4);
 			const int clg = cl + g * NU * BPS;
 #pragma unroll
@@ -1560,6 +1593,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 #pragma unroll
 				for (int ed = 0; ed < NE; ed++) edge_on[ed] = (clg + u * BPS + ed >= 0) && (clg + u * BPS + ed < last);
 				uint32_t res[2][4];
+				uint32_t res8[2][OUT8 ? 2 : 1];      // OUT8: the component's results narrowed
 #pragma unroll
 				for (int c = 0; c < 2; c++)
 				{
@@ -1596,18 +1630,37 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 						else
 							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, t);
 					}
+					if constexpr (OUT8)
+					{
+						narrow(t, res8[c]);
 #pragma unroll
-					for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(rot_down(t[d]), tp[c][d]);
+						for (int d = 0; d < KD; d++) outp[c][DW - KD + d] = lane_down(rot_down(res8[c][d]), tp[c][d]);
+					}
+					else
+					{
+#pragma unroll
+						for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(rot_down(t[d]), tp[c][d]);
+					}
 				}
-				if (u == 0) store_prev(pdst, (NU - 1) * UB);
-				else store_prev(cdst, (u - 1) * UB);
+				if (u == 0) store_prev(pdst, (NU - 1) * UBD);
+				else store_prev(cdst, (u - 1) * UBD);
 #pragma unroll
 				for (int c = 0; c < 2; c++)
 				{
+					if constexpr (OUT8)
+					{
 #pragma unroll
-					for (int d = K; d < 4; d++) outp[c][d - K] = res[c][d];
+						for (int d = KD; d < DW; d++) outp[c][d - KD] = res8[c][d];
 #pragma unroll
-					for (int d = 0; d < K; d++) tp[c][d] = res[c][d];
+						for (int d = 0; d < KD; d++) tp[c][d] = res8[c][d];
+					}
+					else
+					{
+#pragma unroll
+						for (int d = K; d < 4; d++) outp[c][d - K] = res[c][d];
+#pragma unroll
+						for (int d = 0; d < K; d++) tp[c][d] = res[c][d];
+					}
 				}
 #if VFGS_SCHED_FENCE
 				__builtin_amdgcn_sched_barrier(0);
@@ -1626,8 +1679,8 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 #pragma unroll
 	for (int c = 0; c < 2; c++)
 #pragma unroll
-		for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(0u, tp[c][d]);
-	store_prev(pdst, (NU - 1) * UB);
+		for (int d = 0; d < KD; d++) outp[c][DW - KD + d] = lane_down(0u, tp[c][d]);
+	store_prev(pdst, (NU - 1) * UBD);
 }
 
 // The kernels of semi-planar frames (KernelArgs::sp_kernel): the grid and the workgroup numbering of grain_rw_kernel with ONE UV workgroup where
@@ -1647,6 +1700,28 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp_kernel(
 		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
 		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
+}
+
+// The kernels of semi-planar frames with a narrowed destination (KernelArgs::sp_kernel AND out8: P010 / P210 / P012 in, NV12 / NV16 out;
+// vfgs_hip_add_grain_sp_frame_list_copy8_dev): grain_sp_kernel's grid, numbering and residency.  Luma workgroups narrow their results like
+// every OUT8 plane; a UV workgroup narrows each component's planar unit to 8 bytes, rotates the halves back and interleaves them into ONE 16-byte unit
+// of Cb/Cr byte pairs.  The destination has a geometry of its own (PlaneDesc::dpitch, drowbytes: bytes); nothing is ever in place.
+template <int DEPTH, int CSUBY, bool ONEY, bool ONEC>
+__global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp8_kernel(const KernelArgs a, const FrameTable ft)
+{
+	static_assert(DEPTH > 8, "the narrowed destination exists for 16-bit containers");
+	constexpr ImageLayout L = image_layout(2, CSUBY, ONEY, ONEC, false);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[sp_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, ONEC))];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	const int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	if (r < a.pd[0].wgs)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, true, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // The kernels of semi-planar frames under the luma / chroma mix (KernelArgs::sp_kernel AND mix_kernel): all-one-pattern images
@@ -1764,6 +1839,17 @@ static hipError_t launch_sp(const KernelArgs& a, const FrameTable& ft, bool oney
 }
 
 template <int DEPTH, int CSUBY>
+static hipError_t launch_sp8(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	if (oney && onec) hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
+	else if (oney) hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
+	else if (onec) hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
+	else hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
+template <int DEPTH, int CSUBY>
 static hipError_t launch_sp_mix(const KernelArgs& a, const FrameTable& ft, int grid, hipStream_t stream)
 {
 	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
@@ -1777,8 +1863,19 @@ static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int cs
 	if (a.sp_kernel)
 	{
 		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table (the host refuses everything else)
-		if (out8 || wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
+		if (wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
 		if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
+		if (out8)
+		{
+			// (the narrowed destination: 16-bit containers, no mix; a UV row of bytes is half the source row, whole 16-byte units)
+			if (a.mix_kernel || a.pd[1].drowbytes * 2 != a.pd[1].rowbytes || a.pd[0].drowbytes * 2 != a.pd[0].rowbytes) return hipErrorInvalidValue;
+			if constexpr (D > 8)
+			{
+				if (csuby == 2) return launch_sp8<D, 2>(a, ft, oney, onec, grid, stream);
+				if (csuby == 1) return launch_sp8<D, 1>(a, ft, oney, onec, grid, stream);
+			}
+			return hipErrorInvalidValue;
+		}
 		if (a.mix_kernel)
 		{
 			// (the mix: all-one-pattern images at 8 and 10 bit; launch_depth<12> instantiates none, the host refuses such a call before it gets here)

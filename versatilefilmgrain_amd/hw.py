@@ -118,6 +118,7 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_add_grain_frame_list_seeded_copy8_dev.argtypes = [fp, fp, sp, u, u, u, u, u, u, u, vp]
     spf = C.POINTER(SpFrame)
     lib.vfgs_hip_add_grain_sp_frame_list_dev.argtypes = [spf, spf, sp, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_sp_frame_list_copy8_dev.argtypes = [spf, spf, sp, u, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -183,7 +184,7 @@ EXPORTS = [
     "vfgs_hip_dev_build", "vfgs_hip_init_devices", "vfgs_hip_overlap_begin", "vfgs_hip_overlap_end", "vfgs_hip_get_stream_stats", "vfgs_hip_line_lookahead", "vfgs_hip_declare_frame",
     "vfgs_hip_get_stripe_stream_stats", "vfgs_hip_lfsr_segments",
     "vfgs_hip_add_grain_frame_list_seeded_dev", "vfgs_hip_add_grain_frame_list_seeded_part_dev", "vfgs_hip_add_grain_frame_list_seeded_copy_dev",
-    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
+    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_dev", "vfgs_hip_add_grain_sp_frame_list_copy8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
 ]
@@ -336,6 +337,16 @@ class VfgsHip:
         assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
         self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
                                                                sample_shift, stream))
+
+    def add_grain_sp_frame_list_copy8_dev(self, src, dst, seeds, width, height, stride, uv_stride, dst_stride, dst_uv_stride, sample_shift, stream=0):
+        """Semi-planar frames with the narrowed 8-bit destination (P010 / P210 / P012 -> NV12 / NV16): src as in add_grain_sp_frame_list_dev at
+        depth 10 or 12 (strides in 16-bit containers), dst frames of bytes (strides in bytes), never in place; seeds None: one seed sequence.
+        The bytes are the planar copy8 list's on the de-interleaved picture, interleaved again.  Depth 8: VfgsHipError 16; an active chroma
+        mix: 40; a destination that shares bytes with any source plane: 18 (include/vfgs_hip.h)."""
+        s, d = self.sp_frame_list(src), self.sp_frame_list(dst)
+        assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
+        self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_copy8_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
+                                                                     dst_stride, dst_uv_stride, sample_shift, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
