@@ -307,6 +307,54 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
                                                unsigned sample_shift,      /* 0, or 16 - depth */
                                                void* stream);
 
+/* PLANAR frames in, SEMI-PLANAR surfaces out: what a software decoder hands out (vvdec, VTM, libde265, dav1d: yuv420p, yuv420p10le,
+ * yuv422p10le ...) goes onto the NV12 / NV16 / P010 / P210 / P012 surface a display, a compositor or a hardware encoder takes, in ONE pass
+ * instead of the planar copy list into scratch, an interleave pass and a shift-up (or narrowing) pass (measured: 0.12 .. 0.46 of their time
+ * at 1080p x 32 .. 4320p x 8; against the semi-planar call above on the same bytes -3 .. +1 % at 2160p / 4320p to P010, up to +14 % where a
+ * chroma row is under 2 KiB; DESIGN.md 4.7, profiles/planar_to_semiplanar.json).
+ *   src[f]       a planar picture at the programmed depth: Y, U, V with LOW-aligned samples, stride / cstride in samples, exactly as in
+ *                the planar list calls above;
+ *   dst[f]       a semi-planar picture in the depth's container (uint8 at depth 8, uint16 at 10 and 12): Y, and UV with
+ *                UV[2 i] = U[i], UV[2 i + 1] = V[i]; dst_stride, dst_uv_stride in containers, each >= 16 * ceil(width / 16) (a UV row of
+ *                whole blocks is as many containers as the luma row), pitches in bytes multiples of 16, pointers 16-byte aligned;
+ *   sample_shift 0, or 16 - depth (P010: 6, P012: 4); only 0 at depth 8;
+ *   seeds        NULL: one seed sequence; else a seed per picture.
+ * Every written container is the sample vfgs_hip_add_grain_frame_list_copy_dev (with seeds: _seeded_copy_dev) writes for the same position
+ * of src[f], << sample_shift, truncated to the container; the four seed registers afterwards are that call's.  A source container above the
+ * depth's range behaves exactly as in the planar calls.  Only the whole 16-sample blocks of the picture's rows are written; everything
+ * else in the destination keeps its bytes.  One launch per 32 frames (vfgs_hip_last_launch_info(): listed = 1, in_place = 0, out8 = 0,
+ * kernel grain_p2sp_kernel<depth,csuby,oney,onec>); inside an overlap region the call alternates over the two internal streams like
+ * every other device-pointer call.  General-form models (every fgs_sei* configuration) and one-pattern models alike.
+ * Refused before anything changes (a refused call does not reseed): everything the planar list calls refuse for src, with their codes
+ * (18 a null list or plane, 7 a misaligned pointer, 5 / 6 / 8 geometry, ...); for dst what the semi-planar calls refuse, with theirs: 18 a
+ * null list or plane, 7 a misaligned pointer, 6 / 8 a stride too small / a pitch that is no multiple of 16 bytes; error 40 with a message
+ * that names the cause: csubx != 2, a bad sample_shift, width > 8192.  There is no in-place form: a destination plane that shares bytes
+ * with another destination plane or with ANY source plane of the call is error 18.  An active chroma mix: error 40, "chroma mix" in the
+ * message -- the mix needs the luma over a UV row in the UV workgroup's ring (as in grain_sp_mix_kernel) on top of the planar loads, which
+ * is not built; a caller with a mix grains planar with the calls that honour it.  An empty list is no call at all.
+ * Out of scope, on purpose: the mix, stripe / part forms, host-memory entry points, 4:4:4, widths above 8192, and the reverse direction
+ * (a surface in, planes out). */
+int vfgs_hip_add_grain_frame_list_to_sp_dev(const vfgs_hip_frame_ptrs* src,      /* Y, U, V: planar, low-aligned */
+                                            const vfgs_hip_sp_frame* dst,        /* Y, UV */
+                                            const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
+                                            unsigned nframes, unsigned width, unsigned height,
+                                            unsigned stride, unsigned cstride,            /* source, in samples */
+                                            unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in containers */
+                                            unsigned sample_shift,      /* 0, or 16 - depth (P010: 6, P012: 4); 0 only at depth 8 */
+                                            void* stream);
+
+/* ... with the NARROWED 8-BIT DESTINATION: planar 10- or 12-bit pictures in, NV12 / NV16 out.  As above with dst[f] a semi-planar picture
+ * of bytes, dst_stride / dst_uv_stride in BYTES (each >= 16 * ceil(width / 16) and a multiple of 16); the bytes written are those of
+ * vfgs_hip_add_grain_frame_list_copy8_dev (with seeds: _seeded_copy8_dev) on src[f], Cb and Cr interleaved: (uint8)((v + 2) >> 2) at
+ * depth 10, (uint8)((v + 8) >> 4) at depth 12; the seed registers are that call's.  vfgs_hip_last_launch_info(): out8 = 1, kernel
+ * grain_p2sp8_kernel<depth,csuby,oney,onec>.  Refusals as above; depth 8: error 16, as in the planar _copy8 calls. */
+int vfgs_hip_add_grain_frame_list_to_sp8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst,
+                                             const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
+                                             unsigned nframes, unsigned width, unsigned height,
+                                             unsigned stride, unsigned cstride,            /* source, in 16-bit samples */
+                                             unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
+                                             void* stream);
+
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).
  * `out` holds nseg * seg_words 32-bit words.  first_bit is reached by one jump (a 32 x 32 bit matrix, log2(first_bit) squarings),

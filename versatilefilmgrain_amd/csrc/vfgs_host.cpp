@@ -1436,6 +1436,10 @@ struct DstGeom {          // destination geometry when it differs from the sourc
 	bool out8 = false;
 	unsigned stride = 0, cstride = 0;
 	uint64_t ypitch = 0, cpitch = 0;
+	// a planar source with a semi-planar destination (vfgs_hip_add_grain_frame_list_to_sp_dev / _to_sp8_dev): dU == dV is the UV plane, stride / cstride
+	// above are the destination's rows in ITS containers (out8: bytes) and the samples go `p2sp_shift` bits up in them
+	bool p2sp = false;
+	unsigned p2sp_shift = 0;
 };
 
 int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV, unsigned width,
@@ -1450,7 +1454,16 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	if (int e = ensure_init(-1)) return e;
 	if (int e = check_geometry(s, sY, sU, sV, width, stride, cstride)) return e;
 	const bool sp = sp_shift >= 0;
-	if (!dg.out8)
+	const bool p2sp = dg.p2sp;            // planar source, semi-planar destination: `sp` (both semi-planar) is false
+	if (p2sp && !dg.out8)
+	{
+		// (the destination's rows in containers of the source's size: Y, and a UV row as long as it)
+		const unsigned nb = (width + 15) / 16, dsz = s.bs ? 2 : 1;
+		if (dg.stride < nb * 16 || dg.cstride < nb * 16) return fail(6, "destination stride %u/%u too small: whole 16-sample blocks are written (need >= %u/%u)", dg.stride, dg.cstride, nb * 16, nb * 16);
+		if (((uintptr_t)dY | (uintptr_t)dU | (uintptr_t)dV) & 15) return fail(7, "plane pointers must be 16-byte aligned");
+		if ((dg.stride * dsz) % 16 || (dg.cstride * dsz) % 16) return fail(8, "row pitch must be a multiple of 16 bytes");
+	}
+	else if (!dg.out8)
 	{
 		if (int e = check_geometry(s, dY, dU, dV, width, stride, cstride)) return e;
 	}
@@ -1459,13 +1472,15 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		const unsigned nb = (width + 15) / 16;
 		if (s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
 		// (semi-planar frames: a UV row of bytes holds Cb AND Cr of its blocks, as many bytes as the luma row)
-		if (dg.stride < nb * 16 || dg.cstride < (sp ? nb * 16 : nb * 16 / s.csubx)) return fail(6, "destination stride too small");
+		if (dg.stride < nb * 16 || dg.cstride < ((sp || p2sp) ? nb * 16 : nb * 16 / s.csubx)) return fail(6, "destination stride too small");
 		if ((((uintptr_t)dY | (uintptr_t)dU | (uintptr_t)dV) & 15) || dg.stride % 16 || dg.cstride % 16 || (dg.ypitch | dg.cpitch) % 16)
 			return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
 	}
 	if (seeds && (frame_y != 0 || !list)) return fail(19, "internal: seeds belong to lists of frames that begin at line 0");
 	if (sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
+	if (p2sp && (sp || !list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
+		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) return 0;
 	if (int e = check_luts(s)) return e;     // before any state moves: a refused call leaves the seed registers alone
@@ -1476,6 +1491,12 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	const uint64_t yext = (uint64_t)part_h * stride * sz, cext = crows * cstride * sz;
 	if (yext >= 0x80000000ull || cext >= 0x80000000ull)
 		return fail(15, "a plane stripe of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)yext);
+	if (p2sp)
+	{
+		const uint64_t dsz = dg.out8 ? 1 : sz, dyext = (uint64_t)part_h * dg.stride * dsz, dcext = crows * dg.cstride * dsz;
+		if (dyext >= 0x80000000ull || dcext >= 0x80000000ull)
+			return fail(15, "a destination plane of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)std::max(dyext, dcext));
+	}
 	KernelArgs a{};
 	a.src[0] = (const uint8_t*)sY; a.src[1] = (const uint8_t*)sU; a.src[2] = (const uint8_t*)sV;
 	a.dst[0] = (uint8_t*)dY; a.dst[1] = (uint8_t*)dU; a.dst[2] = (uint8_t*)dV;
@@ -1501,6 +1522,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
 	// (the semi-planar call refuses the same cases under its own code, 40: the two entries stay congruent on the planar picture)
 	const bool mix = mix_active();
+	if (mix && p2sp) return fail(19, "internal: a planar source with a semi-planar destination under a chroma mix");     // (refused with code 40 at the entry)
 	const int mix_code = sp ? 40 : 38;
 	const char* const mix_who = sp ? "semi-planar frames: " : "";
 	if (mix && s.bs == 4)
@@ -1520,12 +1542,12 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			const unsigned subx = pt ? s.csubx : 1, suby = pt ? s.csuby : 1;
 			const unsigned bw = 16 / subx, rpb = 16 / suby;
 			d.pitch = (pt ? cstride : stride) * sz;
-			d.dpitch = dg.out8 ? (pt ? dg.cstride : dg.stride) : d.pitch;
+			d.dpitch = dg.out8 ? (pt ? dg.cstride : dg.stride) : (p2sp ? (pt ? dg.cstride : dg.stride) * sz : d.pitch);
 			d.fpitch = pt ? cpitch : ypitch;
 			d.dfpitch = dg.out8 ? (pt ? dg.cpitch : dg.ypitch) : d.fpitch;
 			// (semi-planar frames: "chroma" is the one plane of interleaved Cb/Cr pairs, a row of whole blocks as many containers as a luma row)
 			d.rowbytes = nblk * bw * sz * ((sp && pt) ? 2 : 1);
-			d.drowbytes = dg.out8 ? nblk * bw * ((sp && pt) ? 2 : 1) : d.rowbytes;
+			d.drowbytes = dg.out8 ? nblk * bw * ((sp && pt) ? 2 : 1) : d.rowbytes;      // (p2sp, chroma: ONE component's bytes of the UV row, vfgs_layout.h sp_kernel)
 			d.nrows = pt ? (int)((part_y + part_h + suby - 1) / suby) - (int)((part_y + suby - 1) / suby) : (int)part_h;
 			auto lg = [](int v) { int l = 0; while ((1 << l) < v) l++; return l; };
 			const int ub = (sp && pt) ? vfgs::kSpUnitBytes : 16;   // (a lane's unit of an interleaved row: 32 bytes, vfgs_kernel.hip "UV walk")
@@ -1535,14 +1557,16 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			// (8-bit luma in the general form -- per-sample pattern selection, 24 LDS instructions per position -- does better with
 			// waves of one row: +4 % at 2160p, profiles/r03_ab39_workgroup_bytes_8bit.log; every other form loses 4-7 % with them)
 			const size_t wg_bytes = (pt == 0 && s.bs == 0 && !form_one_y) ? VFGS_RW_WG_BYTES / 2 : VFGS_RW_WG_BYTES;
-			while (vfgs::kWavesPerWG * rpw * 2 <= (int)rpb && (size_t)vfgs::kWavesPerWG * rpw * d.rowbytes < wg_bytes) rpw *= 2;
+			// (p2sp: a UV workgroup moves both components' rows, as many bytes as the workgroup of an interleaved row)
+			const size_t wg_row = (size_t)d.rowbytes * ((p2sp && pt) ? 2 : 1);
+			while (vfgs::kWavesPerWG * rpw * 2 <= (int)rpb && (size_t)vfgs::kWavesPerWG * rpw * wg_row < wg_bytes) rpw *= 2;
 			for (int i = 0; i < rw_shrink && rpw > 1; i++) rpw /= 2;
 			if (nparts > 1) rpw = 1;        // rows walked in parts (more than 512 blocks): the kernel's part loop assumes one row per wave
 			d.rw_rpw = rpw;
 			d.rw_splits = std::max<int>(1, (int)rpb / (vfgs::kWavesPerWG * rpw));
 			d.rw_lsplits = lg(d.rw_splits);
 			d.wgs = d.nrows > 0 ? nbr_stripe * d.rw_splits : 0;
-			waves += (long)((pt && !sp) ? 2 : 1) * d.wgs * vfgs::kWavesPerWG * nframes;
+			waves += (long)((pt && !sp && !p2sp) ? 2 : 1) * d.wgs * vfgs::kWavesPerWG * nframes;
 		}
 		const long slots = (long)s.cu_count * 16;          // wave slots of the chip at the kernels' occupancy
 		if (pass < 2 && waves * 100 < VFGS_RW_MIN_FILL_PCT * slots && (a.pd[0].rw_rpw > 1 || a.pd[1].rw_rpw > 1)) { rw_shrink++; continue; }
@@ -1635,7 +1659,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	}
 
 	// one workgroup per (frame, plane, block row, part of it), numbered in memory order
-	const long per_frame = (long)a.pd[0].wgs + (sp ? 1L : 2L) * a.pd[1].wgs;     // (semi-planar frames: one UV workgroup serves Cb and Cr)
+	const long per_frame = (long)a.pd[0].wgs + ((sp || p2sp) ? 1L : 2L) * a.pd[1].wgs;     // (semi-planar frames: one UV workgroup serves Cb and Cr)
 	if (per_frame > 0x3fffffffL || nframes > 65535) return fail(14, "launch too large");
 	if (per_frame == 0) { if (seeds) seeded_done(); return 0; }
 	// General-form luma of small pictures: a workgroup stages 36 KB of tables for 15-30 KB of samples.  Where a launch holds several
@@ -1645,7 +1669,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	long grid = per_frame;
 	// (10 and 12 bit -- the same bytes through the same LDS image -- only: at 8 bit the general-form kernels are bound by their LDS instructions, and confining luma to P < all workgroup
 	// slots costs them 7 %; at 10 bit 1080p gains 6 % at 32 and 64 frames per launch, 2160p nothing: profiles/r04_ab2_persistent_luma.log)
-	if (VFGS_PERSIST_MIN_TASKS > 0 && !sp && s.bs != 0 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
+	if (VFGS_PERSIST_MIN_TASKS > 0 && !sp && !p2sp && s.bs != 0 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
 	    (size_t)vfgs::kWavesPerWG * a.pd[0].rw_rpw * a.pd[0].rowbytes <= ((size_t)VFGS_PERSIST_MAX_WG_KB << 10))
 	{
 		const long tasks = (long)a.pd[0].wgs * nframes, slots = (long)s.cu_count * 4;     // (general form: four workgroups per CU)
@@ -1673,6 +1697,11 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	{
 		a.sp_kernel = 1;
 		a.sp_shift2 = (uint32_t)sp_shift * 0x10001u;
+	}
+	if (p2sp)
+	{
+		a.sp_kernel = 2;
+		a.sp_shift2 = dg.p2sp_shift * 0x10001u;
 	}
 	if (mix)
 	{
@@ -1755,6 +1784,13 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 				li.lds_bytes_per_workgroup = vfgs::sp_mix_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, true));
 				snprintf(li.kernel, sizeof li.kernel, "grain_sp_mix_kernel<%d,%d>", 8 + s.bs, s.csuby);
 			}
+		}
+		if (p2sp)
+		{
+			// (a planar source, a semi-planar destination: grain_sp_kernel's template arguments, residency and LDS allocation)
+			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, s.img_one_c));
+			snprintf(li.kernel, sizeof li.kernel, "%s<%d,%d,%s,%s>", dg.out8 ? "grain_p2sp8_kernel" : "grain_p2sp_kernel", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false",
+			         s.img_one_c ? "true" : "false");
 		}
 		g_last_launch_valid = true;
 	}
@@ -2919,7 +2955,10 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
                           const int sp_shift = -1)     // >= 0: semi-planar frames, U == V == the UV plane of a frame and cstride its row (run_device)
 {
 	const bool sp = sp_shift >= 0;
-	const int ncomp = sp ? 2 : 3;     // planes of a frame
+	const bool p2sp = dg.p2sp;        // (planar source, semi-planar destination: dst[f].U == dst[f].V is the UV plane)
+	const bool dgeo = dg.out8 || p2sp;
+	const int ncomp = sp ? 2 : 3;     // planes of a source frame ...
+	const int ncomp_d = (sp || p2sp) ? 2 : 3;     // ... and of a destination frame
 	if (whole) { part_y = 0; part_h = height; }
 	State& s = S();
 	if (int e = ensure_init(-1)) return e;
@@ -2939,22 +2978,23 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 	// ANOTHER (that frame may already have been grained when it is read).  The bytes of a plane: its rows of the stripe, whole
 	// 16-sample blocks each (check_geometry).  A frame's own source and destination are either the same plane (in place) or disjoint.
 	// (semi-planar frames with the narrowed destination: containers of another size, so there is no in-place form -- disjoint, always)
-	const bool no_in_place = sp && dg.out8;
+	const bool no_in_place = (sp && dg.out8) || p2sp;
 	{
 		const uint64_t sz = s.bs ? 2 : 1, nblk = (width + 15) / 16;
 		const uint64_t crows = part_h ? (uint64_t)(part_y + part_h - 1) / s.csuby - part_y / s.csuby + 1 : 0;
-		const uint64_t dsz = dg.out8 ? 1 : sz, dstr = dg.out8 ? dg.stride : stride, dcstr = dg.out8 ? dg.cstride : cstride;
+		const uint64_t dsz = dg.out8 ? 1 : sz, dstr = dgeo ? dg.stride : stride, dcstr = dgeo ? dg.cstride : cstride;
 		auto extent = [&](uint64_t rows, uint64_t pitch, uint64_t rowb) { return rows ? (rows - 1) * pitch + rowb : 0; };
 		const uint64_t cblk = sp ? 16 : 16 / s.csubx;     // containers of a grain block in a chroma row (semi-planar: Cb and Cr)
+		const uint64_t cblk_d = p2sp ? 16 : cblk;         // ... of the destination
 		const uint64_t ext_s[3] = {extent(part_h, stride * sz, nblk * 16 * sz), extent(crows, cstride * sz, nblk * cblk * sz), 0};
-		const uint64_t ext_d[3] = {extent(part_h, dstr * dsz, nblk * 16 * dsz), extent(crows, dcstr * dsz, nblk * cblk * dsz), 0};
+		const uint64_t ext_d[3] = {extent(part_h, dstr * dsz, nblk * 16 * dsz), extent(crows, dcstr * dsz, nblk * cblk_d * dsz), 0};
 		struct Span { uintptr_t lo, hi; unsigned frame; };
 		std::vector<Span> d;
 		d.reserve(3 * (size_t)nframes);
 		for (unsigned f = 0; f < nframes; f++)
 		{
 			const void* pl[3] = {dst[f].Y, dst[f].U, dst[f].V};
-			for (int c = 0; c < ncomp; c++) d.push_back({(uintptr_t)pl[c], (uintptr_t)pl[c] + ext_d[c ? 1 : 0], f});
+			for (int c = 0; c < ncomp_d; c++) d.push_back({(uintptr_t)pl[c], (uintptr_t)pl[c] + ext_d[c ? 1 : 0], f});
 		}
 		std::sort(d.begin(), d.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
 		for (size_t i = 1; i < d.size(); i++)
@@ -3140,6 +3180,57 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
 	dg.stride = dst_stride; dg.cstride = dst_uv_stride;
 	return run_frame_list(ps.data(), pd.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), dg, true, 0, 0, seeds != nullptr, seeds,
 	                      (int)sample_shift);
+}
+
+// A planar source, a semi-planar destination (vfgs_hip.h): what a software decoder hands out goes onto the surface a display takes.  The planar
+// list call with a destination geometry of its own whose U and V planes are the UV plane; what the semi-planar calls refuse for their
+// destination is refused here with their codes, before anything moves.
+static int run_to_sp(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height,
+                     unsigned stride, unsigned cstride, unsigned dst_stride, unsigned dst_uv_stride, unsigned sample_shift, bool out8, void* stream)
+{
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	if (s.csubx != 2)
+		return fail(40, "planar to semi-planar: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
+	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
+		return fail(40, "planar to semi-planar: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
+	if (width > (unsigned)vfgs::kTileBlocks * 16)
+		return fail(40, "planar to semi-planar: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
+	if (out8 && s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
+	if (mix_active())
+		return fail(40, "planar to semi-planar: a chroma mix is active; these kernels have no form with the luma over their chroma rows (grain planar with the mix calls)");
+	if (!src || !dst) return fail(18, "frame list: null list");
+	// (the destination's pitches, with the codes of the calls it is carried over from: a UV row is as many containers as the luma row)
+	const unsigned nb16 = (width + 15) / 16 * 16, dsz = (out8 || s.bs == 0) ? 1 : 2;
+	if (dst_stride < nb16 || dst_uv_stride < nb16)
+		return fail(6, "destination stride %u/%u too small: whole 16-sample blocks are written (need >= %u/%u)", dst_stride, dst_uv_stride, nb16, nb16);
+	if ((dst_stride * dsz) % 16 || (dst_uv_stride * dsz) % 16) return fail(8, "destination row pitches must be multiples of 16 bytes");
+	std::vector<vfgs_hip_frame_ptrs> ps(src, src + nframes), pd(nframes);
+	for (unsigned f = 0; f < nframes; f++) pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
+	DstGeom dg;
+	dg.out8 = out8;
+	dg.p2sp = true;
+	dg.p2sp_shift = sample_shift;
+	dg.stride = dst_stride; dg.cstride = dst_uv_stride;
+	return run_frame_list(ps.data(), pd.data(), nframes, width, height, stride, cstride, pick_stream(stream), dg, true, 0, 0, seeds != nullptr, seeds);
+}
+
+int vfgs_hip_add_grain_frame_list_to_sp_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
+                                            unsigned width, unsigned height, unsigned stride, unsigned cstride, unsigned dst_stride,
+                                            unsigned dst_uv_stride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return run_to_sp(src, dst, seeds, nframes, width, height, stride, cstride, dst_stride, dst_uv_stride, sample_shift, false, stream);
+}
+
+int vfgs_hip_add_grain_frame_list_to_sp8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
+                                             unsigned width, unsigned height, unsigned stride, unsigned cstride, unsigned dst_stride,
+                                             unsigned dst_uv_stride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return run_to_sp(src, dst, seeds, nframes, width, height, stride, cstride, dst_stride, dst_uv_stride, 0, true, stream);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,

@@ -30,7 +30,9 @@
 //   * semi-planar frames (a luma plane + ONE plane of interleaved Cb/Cr pairs, samples possibly in the high bits of their containers) have a
 //     kernel family of their own, grain_sp_kernel: the luma walk with a container shift, and a UV walk whose lanes move 32 bytes and split
 //     them into one planar Cb unit and one planar Cr unit ("UV walk" below); with the narrowed 8-bit destination (P010 in, NV12 out): grain_sp8_kernel,
-//     the same two walks with OUT8 -- a UV lane stores ONE 16-byte unit of Cb/Cr byte pairs.
+//     the same two walks with OUT8 -- a UV lane stores ONE 16-byte unit of Cb/Cr byte pairs;
+//   * a PLANAR source with a semi-planar destination (software-decoded pictures onto a display surface): grain_p2sp_kernel / grain_p2sp8_kernel, the same
+//     two walks again -- a UV lane loads one 16-byte unit from the Cb row and one from the Cr row instead of splitting 32 bytes of an interleaved row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -678,7 +680,10 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //   * SP (luma planes of grain_sp_kernel, 16-bit containers): the samples sit KernelArgs::sp_shift2 bits up in their containers; a position's
 //     units are shifted down as they leave the ring and the results up before they go to memory (a packed 16-bit shift per dword each way).
 //     SP with OUT8 (luma planes of grain_sp8_kernel): shifted down the same way, then narrowed like any OUT8 plane and not shifted up.
-template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, bool SP = false>
+//     SP = 2 (luma planes of grain_p2sp_kernel / grain_p2sp8_kernel: a PLANAR source, a semi-planar destination): the source is read as it lies,
+//     low-aligned -- nothing is shifted down -- the results go up or are narrowed as above, and the destination has a geometry of its own
+//     (dpitch, drowbytes) at either container size.
+template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
 {
@@ -706,6 +711,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
+	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
@@ -815,9 +821,9 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	auto row_off = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.pitch); };
 	// (only the narrowed destination has a geometry of its own: otherwise the host passes the source's, and saying so here
 	// saves the scalar registers of a second set of row offsets)
-	auto row_offd = [&](int k) { return OUT8 ? (uint32_t)((base + RSTR * k - prow0) * (int)pd.dpitch) : row_off(k); };
+	auto row_offd = [&](int k) { return DGEO ? (uint32_t)((base + RSTR * k - prow0) * (int)pd.dpitch) : row_off(k); };
 	auto left = [&](int g) { const uint32_t o = (uint32_t)g * GB; return o < pd.rowbytes ? min(pd.rowbytes - o, GB) : 0u; };
-	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD, rb = OUT8 ? pd.drowbytes : pd.rowbytes; return o < rb ? min(rb - o, GBD) : 0u; };
+	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD, rb = DGEO ? pd.drowbytes : pd.rowbytes; return o < rb ? min(rb - o, GBD) : 0u; };
 	uint32_t w[NU][4];
 	// MIX: the luma over my chroma units (row cy * SUBY of the luma plane, SUBX units per chroma unit), in the ring with them
 	constexpr int LQ = MIX ? SUBX : 1;
@@ -1040,7 +1046,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				// assemble my 16 bytes: the last K dwords of the unit of the lane before me, the first 4 - K of mine
 				uint32_t t[4];
 				uint32_t ti[4] = {};
-				if constexpr (SP && DEPTH > 8)
+				if constexpr (SP == 1 && DEPTH > 8)
 				{
 #pragma unroll
 					for (int d = 0; d < 4; d++) w[u][d] = pk_lshr_b16(a.sp_shift2, w[u][d]);
@@ -1297,7 +1303,13 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // issued with the position's own: they are part of the ring.  ONE read of the luma serves both components: mix_index runs on the split Cb
 // unit and on the split Cr unit with the same luma registers, each with its component's multipliers; the index dwords take the samples' lane
 // shift and carry, and grain_unit's LUT gathers read them.
-template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false>
+//
+// PLANAR (UV workgroups of grain_p2sp_kernel / grain_p2sp8_kernel: a planar source, vfgs_hip_add_grain_frame_list_to_sp_dev): a position's load is one
+// 16-byte buffer load from the Cb row and one from the Cr row, each through a descriptor of its own plane (FrameTable::src[1] / [2]; pd.pitch and
+// pd.rowbytes describe ONE component's source row, the range check is per component row) -- the two planar units the split would have produced,
+// low-aligned as they lie: no v_perm_b32, no shift down.  Everything behind the load is the walk above; the destination always has a geometry
+// of its own (pd.dpitch; pd.drowbytes = ONE component's bytes of a destination row, the UV row holds twice as many).
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
@@ -1315,6 +1327,8 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int DW = OUT8 ? 2 : 4;                     // dwords of a component's planar unit in the destination ...
 	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of them belong to the lane before its own
 	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0 && !MIX), "the narrowed destination exists for 16-bit containers, without the mix");
+	static_assert(!PLANAR || !MIX, "a planar source has no mix form");
+	constexpr bool DGEO = OUT8 || PLANAR;                // the destination has a geometry of its own
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
 	constexpr int IMG = sp_uv_image_bytes(CIMG, LUTB, ONE);
@@ -1376,21 +1390,25 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	const int tsegs = pd.rw_segs;
 	const int ngroups = (tsegs + NU - 1) / NU;
 	const uint8_t* sbase = a.listed ? ft.src[1][f] : a.src[1] + (uint64_t)f * pd.fpitch;
+	const uint8_t* sbase2 = PLANAR ? (a.listed ? ft.src[2][f] : a.src[2] + (uint64_t)f * pd.fpitch) : nullptr;     // PLANAR: the Cr plane (sbase: the Cb plane)
 	uint8_t* dbase = a.listed ? ft.dst[1][f] : a.dst[1] + (uint64_t)f * pd.dfpitch;
 	const uint32_t lane32 = (uint32_t)lane * kSpUnitBytes;
-	constexpr uint32_t UB = kMaxUnits * kSpUnitBytes;    // bytes of a position
+	constexpr uint32_t UBI = kMaxUnits * kSpUnitBytes;   // bytes of a position of an interleaved row
+	constexpr uint32_t UB = PLANAR ? kMaxUnits * 16 : UBI;     // bytes of a position of the source (PLANAR: of each component's row)
 	constexpr uint32_t GB = NU * UB;                     // ... of a group
 	auto row_off = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.pitch); };
 	auto left = [&](int g) { const uint32_t o = (uint32_t)g * GB; return o < pd.rowbytes ? min(pd.rowbytes - o, GB) : 0u; };
 	// (only the narrowed destination has a geometry of its own -- run_plane_rw: a lane's two 8-byte planar halves interleave into ONE 16-byte unit of
 	// Cb/Cr byte pairs, a wave access is 1 KiB)
-	constexpr uint32_t UBD = OUT8 ? kMaxUnits * 16 : UB, GBD = NU * UBD;
+	constexpr uint32_t UBD = OUT8 ? kMaxUnits * 16 : UBI, GBD = NU * UBD;
 	auto row_offd = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.dpitch); };
-	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD; return o < pd.drowbytes ? min(pd.drowbytes - o, GBD) : 0u; };
+	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD, rb = PLANAR ? 2 * pd.drowbytes : pd.drowbytes; return o < rb ? min(rb - o, GBD) : 0u; };
 	uint32_t w[NU][8];
-	auto load_pos = [&](const __amdgpu_buffer_rsrc_t rs, const int u) {
-		const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB, 0, LDA);
-		const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB + 16, 0, LDA);
+	// (rs2: PLANAR only -- the Cr row; w[u][0..3] is the Cb unit and w[u][4..7] the Cr unit)
+	auto load_pos = [&](const __amdgpu_buffer_rsrc_t rs, const __amdgpu_buffer_rsrc_t rs2, const int u) {
+		const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rs, PLANAR ? (uint32_t)lane * 16 + u * UB : lane32 + u * UB, 0, LDA);
+		const u32x4 hi = PLANAR ? __builtin_amdgcn_raw_buffer_load_b128(rs2, (uint32_t)lane * 16 + u * UB, 0, LDA)
+		                        : __builtin_amdgcn_raw_buffer_load_b128(rs, lane32 + u * UB + 16, 0, LDA);
 		w[u][0] = lo.x; w[u][1] = lo.y; w[u][2] = lo.z; w[u][3] = lo.w;
 		w[u][4] = hi.x; w[u][5] = hi.y; w[u][6] = hi.z; w[u][7] = hi.w;
 	};
@@ -1408,8 +1426,9 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	};
 	{
 		const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(sbase + (k0 < k1 ? row_off(k0) : 0u), k0 < k1 ? left(0) : 0u);
+		const __amdgpu_buffer_rsrc_t rs02 = PLANAR ? make_rsrc(sbase2 + (k0 < k1 ? row_off(k0) : 0u), k0 < k1 ? left(0) : 0u) : rs0;
 #pragma unroll
-		for (int u = 0; u < NU; u++) load_pos(rs0, u);
+		for (int u = 0; u < NU; u++) load_pos(rs0, rs02, u);
 		if constexpr (MIX)
 		{
 			const __amdgpu_buffer_rsrc_t ls0 = make_rsrc(lbase + (k0 < k1 ? lrow_off(k0) : 0u), k0 < k1 ? left(0) : 0u);
@@ -1542,8 +1561,9 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 			const bool nvalid = !lastg || k + 1 < k1;
 			const uint32_t nso = nvalid ? (lastg ? row_off(k + 1) : ro) + (uint32_t)ng * GB : 0u;
 			const __amdgpu_buffer_rsrc_t nsrc = make_rsrc(sbase + nso, nvalid ? left(ng) : 0u);
+			const __amdgpu_buffer_rsrc_t nsrc2 = PLANAR ? make_rsrc(sbase2 + nso, nvalid ? left(ng) : 0u) : nsrc;
 			const __amdgpu_buffer_rsrc_t nlsrc = make_rsrc(lbase + (MIX && nvalid ? (lastg ? lrow_off(k + 1) : lro) + (uint32_t)ng * GB : 0u), MIX && nvalid ? left(ng) : 0u);
-			const __amdgpu_buffer_rsrc_t cdst = OUT8 ? make_rsrc(dbase + (row_offd(k) + (uint32_t)g * GBD), leftd(g)) : make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
+			const __amdgpu_buffer_rsrc_t cdst = DGEO ? make_rsrc(dbase + (row_offd(k) + (uint32_t)g * GBD), leftd(g)) : make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
 			const uint8_t* pe = lds + idx0 + (uint32_t)(g * NU * BPS * 4);
 			const int clg = cl + g * NU * BPS;
 #pragma unroll
@@ -1552,13 +1572,22 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 				const bool firsts = u == 0 && g == 0;
 				// my 32 bytes as a planar Cb unit and a planar Cr unit, low-aligned samples
 				uint32_t cw[2][4];
-#pragma unroll
-				for (int q = 0; q < 4; q++)
+				if constexpr (PLANAR)
 				{
-					cw[0][q] = __builtin_amdgcn_perm(w[u][2 * q + 1], w[u][2 * q], SPLIT_CB);
-					cw[1][q] = __builtin_amdgcn_perm(w[u][2 * q + 1], w[u][2 * q], SPLIT_CR);
+					// (the units as they were loaded; real copies, as in run_plane_rw: the refill below lands in w[u] itself)
+#pragma unroll
+					for (int q = 0; q < 8; q++) asm volatile("v_mov_b32 %0, %1" : "=v"(cw[q / 4][q % 4]) : "v"(w[u][q]));
 				}
-				if constexpr (DEPTH > 8)
+				else
+				{
+#pragma unroll
+					for (int q = 0; q < 4; q++)
+					{
+						cw[0][q] = __builtin_amdgcn_perm(w[u][2 * q + 1], w[u][2 * q], SPLIT_CB);
+						cw[1][q] = __builtin_amdgcn_perm(w[u][2 * q + 1], w[u][2 * q], SPLIT_CR);
+					}
+				}
+				if constexpr (DEPTH > 8 && !PLANAR)
 				{
 #pragma unroll
 					for (int c = 0; c < 2; c++)
@@ -1586,7 +1615,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 					}
 				}
 				// the registers are free: refill them with the position NU steps ahead
-				load_pos(nsrc, u);
+				load_pos(nsrc, nsrc2, u);
 				if constexpr (MIX) load_luma(nlsrc, u);
 				const bool live = NU * g + u < tsegs;
 				bool edge_on[NE];
@@ -1724,6 +1753,55 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp8_kernel
 		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
+// The kernels of a PLANAR source with a semi-planar destination (KernelArgs::sp_kernel == 2; vfgs_hip_add_grain_frame_list_to_sp_dev):
+// what a software decoder hands out (yuv420p, yuv420p10le, yuv422p10le ...) goes to the surface a display or a hardware encoder takes (NV12, P010 ...)
+// in one pass.  grain_sp_kernel's grid, numbering, table staging and residency.  Luma workgroups read the low-aligned source as it lies and store
+// the results shifted up by sp_shift2 at the destination's own pitch; a UV workgroup loads its Cb unit and its Cr unit from the two planar rows
+// (run_uv_sp PLANAR) and stores them interleaved.  Nothing is ever in place.
+template <int DEPTH, int CSUBY, bool ONEY, bool ONEC>
+__global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_p2sp_kernel(const KernelArgs a, const FrameTable ft)
+{
+	constexpr ImageLayout L = image_layout(2, CSUBY, ONEY, ONEC, DEPTH == 8);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[sp_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, ONEC))];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	const int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	// (the frames are listed, always -- launch_depth refuses anything else -- and saying so here takes the plane pointers of the arguments out of both
+	// walks: kept, their 8-register tuple is live across the UV walk beside the second set of descriptors, gets a stack slot and with it scratch memory
+	// for every dispatch; `b` is a copy in registers, never in memory.  Guard: tests/test_code_object_p2sp_cpu.py, private_segment_fixed_size == 0)
+	KernelArgs b = a;
+	b.listed = 1;
+	if (r < b.pd[0].wgs)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, true>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
+}
+
+// ... with the narrowed 8-bit destination (KernelArgs::sp_kernel == 2 AND out8: planar 10 / 12 bit in, NV12 / NV16 out;
+// vfgs_hip_add_grain_frame_list_to_sp8_dev): grain_sp8_kernel's stores behind the planar loads.
+template <int DEPTH, int CSUBY, bool ONEY, bool ONEC>
+__global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_p2sp8_kernel(const KernelArgs a, const FrameTable ft)
+{
+	static_assert(DEPTH > 8, "the narrowed destination exists for 16-bit containers");
+	constexpr ImageLayout L = image_layout(2, CSUBY, ONEY, ONEC, false);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[sp_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, ONEC))];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	const int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	KernelArgs b = a;
+	b.listed = 1;      // (as in grain_p2sp_kernel)
+	if (r < b.pd[0].wgs)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, true, false, false, false, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true, true>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
+}
+
 // The kernels of semi-planar frames under the luma / chroma mix (KernelArgs::sp_kernel AND mix_kernel): all-one-pattern images
 // only, depths 8 and 10, the grid and the workgroup numbering of grain_sp_kernel.  Luma workgroups are grain_sp_kernel's; a UV workgroup holds
 // the luma over its units in its ring and forms both components' index dwords from it.  KernelArgs::mix_planes switches the workgroups of one
@@ -1850,6 +1928,28 @@ static hipError_t launch_sp8(const KernelArgs& a, const FrameTable& ft, bool one
 }
 
 template <int DEPTH, int CSUBY>
+static hipError_t launch_p2sp(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	if (oney && onec) hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
+	else if (oney) hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
+	else if (onec) hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
+	else hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
+template <int DEPTH, int CSUBY>
+static hipError_t launch_p2sp8(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	if (oney && onec) hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
+	else if (oney) hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
+	else if (onec) hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
+	else hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
+template <int DEPTH, int CSUBY>
 static hipError_t launch_sp_mix(const KernelArgs& a, const FrameTable& ft, int grid, hipStream_t stream)
 {
 	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
@@ -1865,6 +1965,27 @@ static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int cs
 		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table (the host refuses everything else)
 		if (wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
 		if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
+		if (a.sp_kernel == 2)
+		{
+			// a planar source: no mix; pd[1] holds ONE component's bytes of a source row and of a destination row, in whole dwords -- a component's
+			// share of the UV row has the source row's containers (narrowed: as bytes), the luma row likewise
+			const uint32_t div = out8 ? 2 : 1;
+			if (a.mix_kernel || a.pd[1].drowbytes * div != a.pd[1].rowbytes || a.pd[0].drowbytes * div != a.pd[0].rowbytes || a.pd[0].rowbytes != 2 * a.pd[1].rowbytes)
+				return hipErrorInvalidValue;
+			if (out8)
+			{
+				if constexpr (D > 8)
+				{
+					if (csuby == 2) return launch_p2sp8<D, 2>(a, ft, oney, onec, grid, stream);
+					if (csuby == 1) return launch_p2sp8<D, 1>(a, ft, oney, onec, grid, stream);
+				}
+				return hipErrorInvalidValue;
+			}
+			if (csuby == 2) return launch_p2sp<D, 2>(a, ft, oney, onec, grid, stream);
+			if (csuby == 1) return launch_p2sp<D, 1>(a, ft, oney, onec, grid, stream);
+			return hipErrorInvalidValue;
+		}
+		if (a.sp_kernel != 1) return hipErrorInvalidValue;
 		if (out8)
 		{
 			// (the narrowed destination: 16-bit containers, no mix; a UV row of bytes is half the source row, whole 16-byte units)

@@ -289,6 +289,9 @@ struct KernelArgs {
 	int mix[2][4];            // ... Cb, Cr: { luma_mult, chroma_mult, offset << (depth - 8), active }
 	// Semi-planar frames (vfgs_hip_add_grain_sp_frame_list_dev; all zero = the planar kernels of always)
 	int sp_kernel;            // 1: grain_sp_kernel serves the launch: components 1 and 2 are ONE plane of interleaved Cb/Cr pairs, pd[1] describes its row
+	                          // 2: grain_p2sp_kernel (out8: grain_p2sp8_kernel): the SOURCE is planar -- src[1] / src[2] are two planes, pd[1].pitch / rowbytes ONE
+	                          //    component's row -- the destination is such a UV plane: dst[1] == dst[2], pd[1].dpitch its row pitch and pd[1].drowbytes ONE
+	                          //    component's bytes of its row (the row holds twice as many); pd[0].dpitch / drowbytes: the destination's luma row
 	uint32_t sp_shift2;       // ... 16-bit containers: the samples sit this many bits up (P010: 6, P012: 4), in both halves of the dword (a packed 16-bit shift each way)
 };
 

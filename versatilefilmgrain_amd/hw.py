@@ -119,6 +119,8 @@ def load(path: Path | None = None) -> C.CDLL:
     spf = C.POINTER(SpFrame)
     lib.vfgs_hip_add_grain_sp_frame_list_dev.argtypes = [spf, spf, sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_sp_frame_list_copy8_dev.argtypes = [spf, spf, sp, u, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_to_sp_dev.argtypes = [fp, spf, sp, u, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_to_sp8_dev.argtypes = [fp, spf, sp, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -184,7 +186,8 @@ EXPORTS = [
     "vfgs_hip_dev_build", "vfgs_hip_init_devices", "vfgs_hip_overlap_begin", "vfgs_hip_overlap_end", "vfgs_hip_get_stream_stats", "vfgs_hip_line_lookahead", "vfgs_hip_declare_frame",
     "vfgs_hip_get_stripe_stream_stats", "vfgs_hip_lfsr_segments",
     "vfgs_hip_add_grain_frame_list_seeded_dev", "vfgs_hip_add_grain_frame_list_seeded_part_dev", "vfgs_hip_add_grain_frame_list_seeded_copy_dev",
-    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_dev", "vfgs_hip_add_grain_sp_frame_list_copy8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
+    "vfgs_hip_add_grain_frame_list_seeded_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_dev", "vfgs_hip_add_grain_sp_frame_list_copy8_dev",
+    "vfgs_hip_add_grain_frame_list_to_sp_dev", "vfgs_hip_add_grain_frame_list_to_sp8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
 ]
@@ -347,6 +350,25 @@ class VfgsHip:
         assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
         self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_copy8_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
                                                                      dst_stride, dst_uv_stride, sample_shift, stream))
+
+    def add_grain_frame_list_to_sp_dev(self, src, dst, seeds, width, height, stride, cstride, dst_stride, dst_uv_stride, sample_shift, stream=0):
+        """Planar frames in, semi-planar surfaces out (yuv420p10le -> P010, yuv420p -> NV12 ...): src a list of (Y, U, V) addresses of planar,
+        low-aligned pictures (strides in samples), dst a list of (Y, UV) addresses (strides in containers), never in place; seeds None: one
+        seed sequence, else a seed per picture; sample_shift 0 or 16 - depth.  Every container is the planar copy list's sample
+        << sample_shift, Cb and Cr interleaved.  An active chroma mix: VfgsHipError 40; a destination that shares bytes with any source
+        plane: 18 (include/vfgs_hip.h)."""
+        s, d = self.frame_list(src), self.sp_frame_list(dst)
+        assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_to_sp_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, cstride,
+                                                                  dst_stride, dst_uv_stride, sample_shift, stream))
+
+    def add_grain_frame_list_to_sp8_dev(self, src, dst, seeds, width, height, stride, cstride, dst_stride, dst_uv_stride, stream=0):
+        """... with the narrowed 8-bit destination (planar 10 / 12 bit -> NV12 / NV16): dst frames of bytes, strides in bytes; the bytes are
+        the planar copy8 list's, Cb and Cr interleaved.  Depth 8: VfgsHipError 16 (include/vfgs_hip.h)."""
+        s, d = self.frame_list(src), self.sp_frame_list(dst)
+        assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_to_sp8_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, cstride,
+                                                                   dst_stride, dst_uv_stride, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
