@@ -355,6 +355,56 @@ int vfgs_hip_add_grain_frame_list_to_sp8_dev(const vfgs_hip_frame_ptrs* src, con
                                              unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
                                              void* stream);
 
+/* FILM GRAIN MODELS AS DEVICE OBJECTS: a model per picture in one launch.  The programmed state is one per process, as in the reference;
+ * real streams change it between pictures (AV1 film grain parameters are per frame, an FGC SEI may be re-sent for any picture, the
+ * reference's CLI switches models with -c <poc>:<file>, vfgs_main.c:595-644,773-781), and re-programming per picture means one frame per
+ * launch.  A MODEL is a snapshot of the programmed state that lives on the device; the list call below names one per picture.
+ *
+ * vfgs_hip_model_capture snapshots what the hardware layer is programmed with NOW, at the programmed depth and chroma format: pattern
+ * banks, scale and pattern LUTs, scale shift, clip limits -- slots the firmware layer generated on the device included (they never visit
+ * the host) -- into a device-resident table image the model owns, in the form the library would choose for pictures of ordinary width.
+ * Capture changes nothing a later call can observe: not the seed registers, not the programmed state.  So a caller programs and captures
+ * in turn:   vfgs_init_afgs1(&a); vfgs_hip_model_capture(&mA, s);   vfgs_init_sei(&b); vfgs_hip_model_capture(&mB, s); ...
+ * The work is asynchronous on `stream`; a first use of the model on another stream waits for it there (an event, no host wait).  Inside
+ * an overlap region pass the region's stream.  Refused with the codes of the processing calls: an undefined pattern-LUT entry (4), a scale
+ * shift out of range (9); a null `out`: 41.  On failure *out is NULL.
+ * vfgs_hip_model_release (NULL, or a handle released before: no-op) may be called as soon as the call that used the model has returned:
+ * the bytes stay alive until the launches queued so far that read them are done (the buffers of released models wait in a short queue and
+ * serve later captures; the ninth release in a row may wait on the host for the oldest one's readers).  vfgs_hip_shutdown releases what is left.
+ * vfgs_hip_model_info: out[8] = { depth, csubx, csuby, one-pattern luma image 0/1, one-pattern chroma image 0/1, scale_shift as stored
+ * (vfgs_hip_get_params), legal range 0/1, device bytes }; 0, or 41 for a null or released handle. */
+typedef struct vfgs_hip_model vfgs_hip_model;                 /* opaque */
+int  vfgs_hip_model_capture(vfgs_hip_model** out, void* stream);
+void vfgs_hip_model_release(vfgs_hip_model* m);
+int  vfgs_hip_model_info(const vfgs_hip_model* m, int out[8]);
+
+/* The list call with A MODEL PER PICTURE.  src / dst / seeds / geometry exactly as in vfgs_hip_add_grain_frame_list[_seeded]_copy_dev
+ * (src == dst, or dst[f]'s plane == src[f]'s plane: in place; seeds NULL: one seed sequence, frame f + 1 continues frame f's registers;
+ * else a seed per picture); models: host memory, `nframes` handles, read during the call only -- repeats are the normal case.  Samples
+ * written, padding left alone, and the four seed registers afterwards are those of
+ *     for f in list order:
+ *         program the state models[f] was captured from;
+ *         if (seeds) vfgs_set_seed(seeds[f]);
+ *         vfgs_hip_add_grain_frame_list_copy_dev(&src[f], &dst[f], 1, ...)
+ * and the library's own programmed state is UNCHANGED by the call: it stays whatever the caller last programmed.
+ * Launches: one per run of at most 32 consecutive frames whose models' images share their form (one_y, one_c of vfgs_hip_model_info);
+ * a change of form inside the list starts a new launch, a change of anything else -- patterns, LUTs, scale shift, range -- does not.
+ * vfgs_hip_last_launch_info(): listed = 1, kernel grain_ml_kernel<depth,csubx,csuby,oney,onec>, `launches` counts every run.  The frames'
+ * model images travel in the kernel arguments like their plane pointers: no copy is queued in front of a launch on account of models.
+ * Inside an overlap region the call alternates over the two internal streams like every device-pointer call; it runs on the primary device.
+ * Refused before anything changes (a refused call does not reseed): everything the list calls refuse, with their codes (18 a null list or
+ * plane, planes that share bytes; 7; 5 / 6 / 8 / 17 geometry; 15) -- except that the scale shift that counts is each model's, checked at
+ * capture, and that a null `seeds` selects the single seed sequence (no error 39) -- and, error 41 with a message that names the cause:
+ * models == NULL, or a NULL or released entry; a model captured at another depth or chroma format than the programmed one; width > 8192
+ * (rows walked in parts); an active chroma mix ("chroma mix" in the message).  An empty list is no call at all.
+ * Out of scope, on purpose: the mix per model, the narrowed 8-bit destination, stripe / part forms, semi-planar surfaces, host-memory
+ * entry points, widths above 8192, persistent luma workgroups (1080p general-form luma runs without them here). */
+int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
+                                             const vfgs_hip_model* const* models,     /* nframes entries */
+                                             const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
+                                             unsigned nframes, unsigned width, unsigned height,
+                                             unsigned stride, unsigned cstride, void* stream);
+
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).
  * `out` holds nseg * seg_words 32-bit words.  first_bit is reached by one jump (a 32 x 32 bit matrix, log2(first_bit) squarings),

@@ -1,0 +1,201 @@
+#!/usr/bin/env python3
+"""Developer tool: what a model per picture costs a frame-list launch, and what it saves, on one MI355X, in one command.
+
+Legs, alternated, `--rounds` rounds, HIP-event windows of `--window` launches after a warm-up, in place, every frame an allocation of
+its own, one seed sequence:
+  a  vfgs_hip_add_grain_frame_list_dev, one programmed model -- from the library given with --parent-lib (the parent commit's build, loaded
+     beside this one: the yardstick whose code no change here touches); without the option, this library's
+  b  vfgs_hip_add_grain_frame_list_models_dev with that same model on every frame: the price of the mechanism (and, where leg a runs
+     persistent luma workgroups, of giving them up)
+  c  the models call with two models of one form alternating (the second: the first with halved scale LUTs and the other range)
+  e  leg a's call through THIS library (with --parent-lib: what separates the two builds from the two entry points)
+  d  today's alternative to c: vfgs_init_sei / vfgs_init_afgs1 + vfgs_hip_add_grain_frame_dev per frame, two recorded configurations
+     (tests/golden/fwcfg) alternating -- pattern generation on the device, a table build and an upload per picture
+Prints one JSON document (profiles/model_list.json is one)."""
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import vfgs_testlib as T  # noqa: E402
+from versatilefilmgrain_amd import fw, hw  # noqa: E402
+
+SHAPES = [  # name, width, height, configuration of legs a-c (and d), second configuration of leg d, frames per launch
+    ("1920x1080 10-bit 4:2:0 fgs_sei x32", 1920, 1080, "fgs_sei_10_420", "fgs_afgs1_test1_10_420", 32),
+    ("3840x2160 10-bit 4:2:0 fgs_afgs1_test1 x16", 3840, 2160, "fgs_afgs1_test1_10_420", "fgs_sei_10_420", 16),
+    ("7680x4320 10-bit 4:2:0 fgs_sei x8", 7680, 4320, "fgs_sei_10_420", "fgs_afgs1_test1_10_420", 8),
+    ("3840x2160 8-bit 4:4:4 fgs_afgs1_test1 x8", 3840, 2160, "fgs_afgs1_test1_8_444", "fgs_sei_ff_test6_8_444", 8),
+]
+
+
+class ParentLib:
+    """the few entry points leg a needs, from another build of the library loaded beside this one (a state of its own)"""
+
+    def __init__(self, path):
+        self.lib = C.CDLL(str(path))
+        vp, u, i = C.c_void_p, C.c_uint, C.c_int
+        for n, a in (("vfgs_set_luma_pattern", [i, vp]), ("vfgs_set_chroma_pattern", [i, vp]), ("vfgs_set_scale_lut", [i, vp]), ("vfgs_set_pattern_lut", [i, vp]),
+                     ("vfgs_set_seed", [u]), ("vfgs_set_scale_shift", [i]), ("vfgs_set_depth", [i]), ("vfgs_set_legal_range", [i]),
+                     ("vfgs_set_chroma_subsampling", [i, i]), ("vfgs_hip_init", [i]),
+                     ("vfgs_hip_add_grain_frame_list_dev", [C.POINTER(hw.FramePtrs), u, u, u, u, u, vp]), ("vfgs_hip_last_launch_info", [C.POINTER(hw.LaunchInfo)])):
+            getattr(self.lib, n).argtypes = a
+        self.lib.vfgs_hip_last_error_string.restype = C.c_char_p
+        assert self.lib.vfgs_hip_init(0) == 0
+        b = hw._b
+        self.set_luma_pattern = lambda k, P: self.lib.vfgs_set_luma_pattern(k, b(P))
+        self.set_chroma_pattern = lambda k, P: self.lib.vfgs_set_chroma_pattern(k, b(P))
+        self.set_scale_lut = lambda c, l: self.lib.vfgs_set_scale_lut(c, b(l))
+        self.set_pattern_lut = lambda c, l: self.lib.vfgs_set_pattern_lut(c, b(l))
+        self.set_seed = lambda s: self.lib.vfgs_set_seed(s & 0xFFFFFFFF)
+        self.set_scale_shift = self.lib.vfgs_set_scale_shift
+        self.set_depth = self.lib.vfgs_set_depth
+        self.set_legal_range = self.lib.vfgs_set_legal_range
+        self.set_chroma_subsampling = self.lib.vfgs_set_chroma_subsampling
+
+    def kernel(self):
+        li = hw.LaunchInfo()
+        return li.kernel.decode() if self.lib.vfgs_hip_last_launch_info(C.byref(li)) == 0 else None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--window", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--pool-mb", type=int, default=1600, help="bytes of frames cycled through per shape (beyond the last-level cache)")
+    ap.add_argument("--shapes", default="0,1,2,3")
+    ap.add_argument("--order", default="abced", help="the legs of a round, in this order (a permutation of abced)")
+    ap.add_argument("--parent-lib", default=None, help="libvfgs_hip.so of the parent commit, for leg a")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    assert sorted(args.order) == sorted("abced"), "--order: a permutation of abced"
+    hip = hw.VfgsHip(device=0)
+    lib = hip.lib
+    parent = ParentLib(args.parent_lib) if args.parent_lib else None
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    out = {"what": "frame lists with a model per picture: legs alternated in one command on one MI355X, %d rounds, HIP-event windows of %d launches after "
+                   "%d warm-up launches, in place, every frame an allocation of its own, uniform random content, one seed sequence "
+                   "(tools/model_list_bench.py), legs in the order %s" % (args.rounds, args.window, args.warmup, args.order),
+           "legs": {"a": "vfgs_hip_add_grain_frame_list_dev, one model, " + ("the parent commit's library" if parent else "THIS library (no --parent-lib)"),
+                    "b": "vfgs_hip_add_grain_frame_list_models_dev, that model on every frame",
+                    "c": "vfgs_hip_add_grain_frame_list_models_dev, two models of one form alternating",
+                    "e": "vfgs_hip_add_grain_frame_list_dev, one model, this library",
+                    "d": "vfgs_init_sei / vfgs_init_afgs1 + vfgs_hip_add_grain_frame_dev per frame, two configurations alternating"},
+           "device": hip.device_info(), "shapes": {}}
+    rng = np.random.default_rng(1)
+    for si in [int(x) for x in args.shapes.split(",")]:
+        name, w, h, cfg_a, cfg_b, nf = SHAPES[si]
+        rec = T.load_trace(cfg_a)
+        depth, sx, sy = T.trace_geometry(rec)
+        lib.vfgs_hip_reset_state()
+        T.replay(hip, rec)
+        m_a = hip.model_capture(sp)
+        for c in range(3):
+            hip.set_scale_lut(c, bytes(v >> 1 for v in hip.luts(c)[0]))
+        hip.set_legal_range(0 if hip.params()["ymin"] else 1)
+        m_b = hip.model_capture(sp)
+        ia, ib = hip.model_info(m_a), hip.model_info(m_b)
+        assert (ia["one_y"], ia["one_c"]) == (ib["one_y"], ib["one_c"]), (ia, ib)
+        lib.vfgs_hip_reset_state()
+        T.replay(hip, rec)
+        if parent:
+            T.replay(parent, rec)
+        structs = []
+        for n in (cfg_a, cfg_b):
+            assert T.trace_geometry(T.load_trace(n)) == (depth, sx, sy)
+            kind, raw = T.load_fwcfg(n)[1][-1]
+            structs.append(fw.struct_from_bytes(kind, raw))
+        sz = 2 if depth > 8 else 1
+        frame_bytes = (w * h + 2 * (w // sx) * (h // sy)) * sz
+        nsets = max(2, -(-args.pool_mb * (1 << 20) // (frame_bytes * nf)))
+        keep, sets, singles = [], [], []
+        dt, top = (torch.int16, 1 << 10) if depth > 8 else (torch.uint8, 256)
+        for _ in range(nsets):
+            ptrs = []
+            for _ in range(nf):
+                planes = [torch.randint(0, top, (rows, cols), dtype=dt, device="cuda") for rows, cols in ((h, w), (h // sy, w // sx), (h // sy, w // sx))]
+                keep.append(planes)
+                ptrs.append(tuple(p.data_ptr() for p in planes))
+            ptrs = [ptrs[i] for i in rng.permutation(nf)]          # list order is not address order
+            sets.append(hip.frame_list(ptrs))
+            singles.append(ptrs)
+        torch.cuda.synchronize()
+        ncalls = args.warmup + args.window
+        cw = w // sx
+        same = (C.c_void_p * nf)(*([m_a] * nf))
+        alt = (C.c_void_p * nf)(*[m_b if i & 1 else m_a for i in range(nf)])
+        la = parent.lib if parent else lib
+
+        def leg_a(k):
+            return la.vfgs_hip_add_grain_frame_list_dev(sets[k % nsets], nf, w, h, w, cw, sp)
+
+        def leg_b(k):
+            return lib.vfgs_hip_add_grain_frame_list_models_dev(sets[k % nsets], sets[k % nsets], same, None, nf, w, h, w, cw, sp)
+
+        def leg_c(k):
+            return lib.vfgs_hip_add_grain_frame_list_models_dev(sets[k % nsets], sets[k % nsets], alt, None, nf, w, h, w, cw, sp)
+
+        def leg_e(k):
+            return lib.vfgs_hip_add_grain_frame_list_dev(sets[k % nsets], nf, w, h, w, cw, sp)
+
+        def leg_d(k):
+            rc = 0
+            for i, (y, u, v) in enumerate(singles[k % nsets]):
+                fw.init(structs[i & 1])
+                rc |= lib.vfgs_hip_add_grain_frame_dev(y, u, v, w, h, w, cw, sp)
+            return rc
+
+        def window(leg, n_warm, n_win):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for k in range(n_warm):
+                assert leg(k) == 0, (la if leg is leg_a else lib).vfgs_hip_last_error_string()
+            stream.synchronize()
+            e0.record(stream)
+            for k in range(n_warm, n_warm + n_win):
+                assert leg(k) == 0, (la if leg is leg_a else lib).vfgs_hip_last_error_string()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / (n_win * nf)
+
+        us = {k: [] for k in "abced"}
+        kernels = {}
+        for _ in range(args.rounds):
+            for key, leg in [(k, {"a": leg_a, "b": leg_b, "c": leg_c, "e": leg_e, "d": leg_d}[k]) for k in args.order]:
+                # (leg d is a launch per FRAME: a window of as many launches as the others, not of nf times as many)
+                nw, nn = (args.warmup, args.window) if key != "d" else (max(1, args.warmup // nf), max(2, args.window // nf))
+                us[key].append(round(window(leg, nw, nn), 3))
+                kernels[key] = parent.kernel() if (key == "a" and parent) else hip.last_launch_info()["kernel"]
+            # leg d leaves this library programmed with a firmware configuration: back to the trace's state for legs that read it
+            lib.vfgs_hip_reset_state()
+            T.replay(hip, rec)
+        med = {k: statistics.median(v) for k, v in us.items()}
+        rngs = {k: [min(v), max(v)] for k, v in us.items()}
+        traffic = frame_bytes * 2      # every sample read once and written once
+        r = {"us_per_frame": us, "kernel": kernels, "median": {k: round(v, 3) for k, v in med.items()}, "min_max": rngs,
+             "fraction_of_8TBs_peak_at_median": {k: round(traffic / (med[k] * 1e-6) / 8e12, 3) for k in med},
+             "b_over_a_ratio_of_medians": round(med["b"] / med["a"], 4), "b_over_e_ratio_of_medians": round(med["b"] / med["e"], 4),
+             "e_over_a_ratio_of_medians": round(med["e"] / med["a"], 4), "c_over_b_ratio_of_medians": round(med["c"] / med["b"], 4),
+             "d_over_c_ratio_of_medians": round(med["d"] / med["c"], 4),
+             "b_inside_a_spread_plus_3_percent": rngs["a"][0] * 0.97 <= med["b"] <= rngs["a"][1] * 1.03,
+             "c_spread_entirely_below_d_spread": rngs["c"][1] < rngs["d"][0],
+             "model_device_bytes": ia["device_bytes"], "model_form": [ia["one_y"], ia["one_c"]], "frame_sets_cycled": nsets}
+        out["shapes"][name] = r
+        print(name, json.dumps(r), file=sys.stderr, flush=True)
+        hip.model_release(m_a)
+        hip.model_release(m_b)
+        del keep, sets, singles
+        torch.cuda.empty_cache()
+    lib.vfgs_hip_reset_state()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -1404,7 +1404,8 @@ StripePlan advance_seeds(State& s, unsigned y, unsigned n, unsigned nblk, unsign
 	return p;
 }
 
-int check_geometry(const State& s, const void* dY, const void* dU, const void* dV, unsigned width, unsigned stride, unsigned cstride)
+int check_geometry(const State& s, const void* dY, const void* dU, const void* dV, unsigned width, unsigned stride, unsigned cstride,
+                   const bool programmed_shift = true)     // false: a call with captured models -- their scale shifts were checked at capture
 {
 	const unsigned sz = s.bs ? 2 : 1;
 	const unsigned nblk = (width + 15) / 16;
@@ -1418,7 +1419,7 @@ int check_geometry(const State& s, const void* dY, const void* dU, const void* d
 		return fail(7, "plane pointers must be 16-byte aligned");
 	if ((stride * sz) % 16 || (cstride * sz) % 16)
 		return fail(8, "row pitch must be a multiple of 16 bytes");
-	if (s.scale_shift + s.bs < 8 || s.scale_shift + s.bs > 13)   // vfgs_hw.c:170
+	if (programmed_shift && (s.scale_shift + s.bs < 8 || s.scale_shift + s.bs > 13))   // vfgs_hw.c:170
 		return fail(9, "scale_shift out of range (vfgs_hw.c:170)");
 	return 0;
 }
@@ -1429,6 +1430,60 @@ void load_seed(State& s, uint32_t seed)
 	s.lfsr.reseed(seed << 1);   // vfgs_hw.c:343
 	s.seed_epoch++;             // (the replicas of vfgs_hip_init_devices resynchronise; StripeStream's chain dies with the cache's epoch)
 	s.rnd = s.rnd_up = s.line_rnd = s.line_rnd_up = 0;
+}
+
+// ------------------------------------------------------------------------------------
+// models as objects (vfgs_hip_model_capture; vfgs_hip_add_grain_frame_list_models_dev)
+//
+// A model is a snapshot of the programmed state as a device image of its own: a vfgs::ModelRecord (clip bounds, the packed form's shift)
+// followed by the table image in the form image_form() chooses for ordinary rows.  The image is uploaded on the stream of the capture;
+// its SlotGuard makes a first use on another stream wait for that upload (an event, no host wait) and remembers the streams that read it.
+// A released model's buffers go to a short queue with the events of those streams: they are handed to a later capture, or freed, only
+// after every launch queued before the release is done.
+}  // namespace
+
+struct vfgs_hip_model {
+	uint8_t* dev = nullptr;       // record + image (the FIRST member: the sanitizer walks, tests/sanitize_models, read the bytes behind it)
+	uint8_t* host = nullptr;      // pinned source of the upload
+	int bs = 0, csubx = 2, csuby = 2;
+	bool one_y = false, one_c = false;
+	int scale_shift = 0, legal = 0;
+	vfgs::ModelRecord rec{};
+	size_t cap = 0, bytes = 0;
+	SlotGuard guard;
+};
+
+namespace {
+
+struct ModelRun {                 // what run_device needs to know about the models of ONE launch: their common form, and frame 0's record
+	bool one_y, one_c;
+	vfgs::ModelRecord first;
+};
+
+std::vector<vfgs_hip_model*> g_models;        // live models (a handle that is not in here is refused, or ignored by release)
+std::vector<vfgs_hip_model*> g_models_left;   // released, oldest first: buffers that queued launches may still read
+constexpr size_t kModelsLeftMax = 8;
+
+bool model_live(const vfgs_hip_model* m)
+{
+	return m && std::find(g_models.begin(), g_models.end(), m) != g_models.end();
+}
+
+void model_destroy(vfgs_hip_model* m)         // (its readers are done)
+{
+	if (m->dev) (void)hipFree(m->dev);
+	if (m->host) (void)hipHostFree(m->host);
+	m->guard.destroy();
+	delete m;
+}
+
+// shutdown of the primary device (the device is idle): everything that is left
+void release_models()
+{
+	for (vfgs_hip_model* m : g_models) model_destroy(m);
+	for (vfgs_hip_model* m : g_models_left) model_destroy(m);
+	g_models.clear();
+	g_models_left.clear();
 }
 
 // Core: launch the kernel over `nframes` frames, lines [part_y, part_y+part_h) of each.
@@ -1447,12 +1502,13 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
                unsigned nframes, uint64_t ypitch, uint64_t cpitch, hipStream_t stream, DstGeom dg = DstGeom(),
                const vfgs::FrameTable* list = nullptr,     // list: the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
                const uint32_t* seeds = nullptr,            // seeds: frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
-               const int sp_shift = -1)                    // >= 0: semi-planar frames (sU == sV, dU == dV: the UV plane, cstride its row in containers), samples that many bits up
+               const int sp_shift = -1,                    // >= 0: semi-planar frames (sU == sV, dU == dV: the UV plane, cstride its row in containers), samples that many bits up
+               const ModelRun* mr = nullptr)               // a model per frame (run_frame_list_models): list->model[] holds their images, the programmed state's image stays out of it
 {
 	State& s = S();
 	if (list && nframes > (unsigned)vfgs::kListFrames) return fail(19, "internal: a listed launch holds at most %d frames", vfgs::kListFrames);
 	if (int e = ensure_init(-1)) return e;
-	if (int e = check_geometry(s, sY, sU, sV, width, stride, cstride)) return e;
+	if (int e = check_geometry(s, sY, sU, sV, width, stride, cstride, !mr)) return e;
 	const bool sp = sp_shift >= 0;
 	const bool p2sp = dg.p2sp;            // planar source, semi-planar destination: `sp` (both semi-planar) is false
 	if (p2sp && !dg.out8)
@@ -1465,7 +1521,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	}
 	else if (!dg.out8)
 	{
-		if (int e = check_geometry(s, dY, dU, dV, width, stride, cstride)) return e;
+		if (int e = check_geometry(s, dY, dU, dV, width, stride, cstride, !mr)) return e;
 	}
 	else
 	{
@@ -1481,9 +1537,12 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (p2sp && (sp || !list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
+	if (mr && (!list || sp || p2sp || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
+		return fail(19, "internal: a model per frame goes with listed whole planar frames of at most %d samples a row, without a chroma mix", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) return 0;
-	if (int e = check_luts(s)) return e;     // before any state moves: a refused call leaves the seed registers alone
+	if (!mr)
+		if (int e = check_luts(s)) return e;     // before any state moves: a refused call leaves the seed registers alone
 
 	const unsigned nblk = (width + 15) / 16;
 	const unsigned sz = s.bs ? 2 : 1;
@@ -1517,7 +1576,8 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	bool form_one_y = false, form_one_c = false;   // the form the table image will have (upload_tables below)
 	digest_pluts(s);
 	const bool wide = nparts > 1;           // rows walked in parts: not every form of the table image has such a kernel (image_form)
-	if (image_is_current(s, wide)) { form_one_y = s.img_one_y; form_one_c = s.img_one_c; }
+	if (mr) { form_one_y = mr->one_y; form_one_c = mr->one_c; }     // (the form the run's models were captured in)
+	else if (image_is_current(s, wide)) { form_one_y = s.img_one_y; form_one_c = s.img_one_c; }
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
 	// (the semi-planar call refuses the same cases under its own code, 40: the two entries stay congruent on the planar picture)
@@ -1610,9 +1670,22 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	}
 	// Images are uploaded on the stream of the call that needs them first; a call on ANOTHER stream waits (once) for that
 	// upload, and a slot is only overwritten after all its readers (SlotGuard)
-	if (int e = upload_tables(s, stream, wide)) return e;
-	HIP_TRY(s.tables_ring.use(stream));
-	a.tables = (const uint8_t*)s.tables_ring.current();
+	if (mr)
+	{
+		// (the images are the models' own, made visible to `stream` by run_frame_list_models; the programmed state's image is neither built nor looked at)
+		a.models_kernel = 1;
+		a.tables = list->model[0] + vfgs::kModelRecordBytes;
+		a.lo2[0] = mr->first.lo2[0]; a.lo2[1] = mr->first.lo2[1]; a.hi2[0] = mr->first.hi2[0]; a.hi2[1] = mr->first.hi2[1];
+		a.pk_shift = mr->first.pk_shift;
+	}
+	else
+	{
+		if (int e = upload_tables(s, stream, wide)) return e;
+		HIP_TRY(s.tables_ring.use(stream));
+		a.tables = (const uint8_t*)s.tables_ring.current();
+	}
+	// the form of the image(s) this launch reads
+	const bool img_one_y = mr ? mr->one_y : s.img_one_y, img_one_c = mr ? mr->one_c : s.img_one_c;
 	// A batch of stripes that are a small part of their frames (a rank of a stripe split) reads short runs of the
 	// stream that lie a whole frame apart: those runs alone, each the jump of the one before (StripeStream).  One segment =
 	// [a word in front of the row above the stripe's first, 64 bits behind its last block].
@@ -1669,7 +1742,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	long grid = per_frame;
 	// (10 and 12 bit -- the same bytes through the same LDS image -- only: at 8 bit the general-form kernels are bound by their LDS instructions, and confining luma to P < all workgroup
 	// slots costs them 7 %; at 10 bit 1080p gains 6 % at 32 and 64 frames per launch, 2160p nothing: profiles/r04_ab2_persistent_luma.log)
-	if (VFGS_PERSIST_MIN_TASKS > 0 && !sp && !p2sp && s.bs != 0 && !wide && !s.img_one_y && a.pd[0].wgs > 0 &&
+	if (VFGS_PERSIST_MIN_TASKS > 0 && !sp && !p2sp && !mr && s.bs != 0 && !wide && !img_one_y && a.pd[0].wgs > 0 &&
 	    (size_t)vfgs::kWavesPerWG * a.pd[0].rw_rpw * a.pd[0].rowbytes <= ((size_t)VFGS_PERSIST_MAX_WG_KB << 10))
 	{
 		const long tasks = (long)a.pd[0].wgs * nframes, slots = (long)s.cu_count * 4;     // (general form: four workgroups per CU)
@@ -1706,7 +1779,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	if (mix)
 	{
 		// (semi-planar frames: grain_sp_mix_kernel, whose UV workgroups read the luma over their rows; the same two-launch rule)
-		if (!(s.img_one_y && s.img_one_c) || persist) return fail(19, "internal: the table image is not the form the chroma mix was admitted for");
+		if (!(img_one_y && img_one_c) || persist) return fail(19, "internal: the table image is not the form the chroma mix was admitted for");
 		a.mix_kernel = 1;
 		a.mix_lw = (int)width;
 		for (int c = 0; c < 2; c++)
@@ -1734,7 +1807,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 			a.mix_planes = 2;      // luma only
 		}
 	}
-	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist, (int)grid, stream));
+	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist, (int)grid, stream));
 	if (seeds) seeded_done();
 	// the stream of the batches behind this one, while the GPU works on this one.  (Failing to work ahead is not a failure of THIS call, which is
 	// queued and whose registers have moved: the next call then builds its image in its own stream.)
@@ -1746,7 +1819,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		li = vfgs_hip_launch_info{};
 		li.launches = n;
 		li.depth = 8 + s.bs; li.csubx = s.csubx; li.csuby = s.csuby;
-		li.out8 = dg.out8; li.one_y = s.img_one_y; li.one_c = s.img_one_c;
+		li.out8 = dg.out8; li.one_y = img_one_y; li.one_c = img_one_c;
 		li.in_place = (sY == dY && sU == dU && sV == dV);
 		li.listed = a.listed;
 		li.internal = g_internal_launch ? 1 : 0;
@@ -1761,9 +1834,11 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		li.parts_per_row = (int)nparts;
 		li.persistent_luma_workgroups = persist ? a.persist_wgs : 0;
 		li.waves_per_workgroup = vfgs::kWavesPerWG;
-		const vfgs::ImageLayout L = vfgs::layout_of(s.csubx, s.csuby, s.img_one_y, s.img_one_c, s.bs == 0);
-		li.lds_bytes_per_workgroup = vfgs::lds_allocation(s.bs != 0, s.img_one_y, s.img_one_c, wide, L.lds_bytes + vfgs::kParamBytes);     // (what the kernel allocates)
-		vfgs::describe_launch(li.kernel, sizeof li.kernel, 8 + s.bs, s.csubx, s.csuby, dg.out8, s.img_one_y, s.img_one_c, wide, persist);
+		const vfgs::ImageLayout L = vfgs::layout_of(s.csubx, s.csuby, img_one_y, img_one_c, s.bs == 0);
+		li.lds_bytes_per_workgroup = vfgs::lds_allocation(s.bs != 0, img_one_y, img_one_c, wide, L.lds_bytes + vfgs::kParamBytes);     // (what the kernel allocates)
+		vfgs::describe_launch(li.kernel, sizeof li.kernel, 8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist);
+		if (mr)     // (a model per frame: depth, chroma subsampling x / y, one-pattern luma, one-pattern chroma; the LDS allocation of its grain_rw_kernel twin, above)
+			snprintf(li.kernel, sizeof li.kernel, "grain_ml_kernel<%d,%d,%d,%s,%s>", 8 + s.bs, s.csubx, s.csuby, img_one_y ? "true" : "false", img_one_c ? "true" : "false");
 		if (mix)
 		{
 			// (the kernels of the mix: depth, chroma subsampling x / y, 8-bit destination, rows walked in parts; `launches` counts both launches of an in-place call)
@@ -2540,6 +2615,7 @@ void release_state_impl(State& s)
 	if (!s.inited) return;
 	(void)fw_flush(s, s.own_stream);
 	(void)hipDeviceSynchronize();
+	if (&s == &g_states[0]) release_models();     // (captured models are the primary device's: vfgs_hip_shutdown releases what the caller has not)
 	// device-generated patterns move to the host mirror so the programmed state survives
 	for (int c = 0; c < 2; c++)
 		for (int k = 0; k < vfgs::kSlots; k++)
@@ -2952,7 +3028,8 @@ int vfgs_hip_add_grain_frames_part_dev(void* dY, void* dU, void* dV, unsigned wi
 static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, unsigned nframes, unsigned width, unsigned height,
                           unsigned stride, unsigned cstride, hipStream_t stream, DstGeom dg, bool whole = true, unsigned part_y = 0, unsigned part_h = 0,
                           bool seeded = false, const uint32_t* seeds = nullptr,     // seeded: frame f is the frame behind vfgs_set_seed(seeds[f])
-                          const int sp_shift = -1)     // >= 0: semi-planar frames, U == V == the UV plane of a frame and cstride its row (run_device)
+                          const int sp_shift = -1,     // >= 0: semi-planar frames, U == V == the UV plane of a frame and cstride its row (run_device)
+                          const vfgs_hip_model* const* models = nullptr)     // a live model of the programmed depth and chroma format per frame (vfgs_hip_add_grain_frame_list_models_dev)
 {
 	const bool sp = sp_shift >= 0;
 	const bool p2sp = dg.p2sp;        // (planar source, semi-planar destination: dst[f].U == dst[f].V is the UV plane)
@@ -2968,7 +3045,7 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 	for (unsigned f = 0; f < nframes; f++)
 	{
 		if (!src[f].Y || !src[f].U || !src[f].V || !dst[f].Y || !dst[f].U || !dst[f].V) return fail(18, "frame list: frame %u has a null plane", f);
-		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride)) return e;
+		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride, !models)) return e;
 		if ((((uintptr_t)dst[f].Y | (uintptr_t)dst[f].U | (uintptr_t)dst[f].V) & 15)) return fail(7, "plane pointers must be 16-byte aligned");
 	}
 	if (sp && cstride < (width + 15) / 16 * 16)
@@ -3016,9 +3093,20 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			}
 		}
 	}
-	for (unsigned f0 = 0; f0 < nframes; f0 += vfgs::kListFrames)
+	if (models)
 	{
-		const unsigned n = std::min<unsigned>(vfgs::kListFrames, nframes - f0);
+		// (what run_device would only find behind the first launch of a list of several: refused here, before anything moves)
+		const uint64_t sz = s.bs ? 2 : 1, crows = ((uint64_t)height + s.csuby - 1) / s.csuby;
+		if ((uint64_t)height * stride * sz >= 0x80000000ull || crows * cstride * sz >= 0x80000000ull)
+			return fail(15, "a plane of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)std::max((uint64_t)height * stride * sz, crows * cstride * sz));
+	}
+	for (unsigned f0 = 0, n = 0; f0 < nframes; f0 += n)
+	{
+		// one launch: kListFrames frames at most -- with a model per frame, a run of frames whose models share the form of their images
+		n = std::min<unsigned>(vfgs::kListFrames, nframes - f0);
+		if (models)
+			for (unsigned k = 1; k < n; k++)
+				if (models[f0 + k]->one_y != models[f0]->one_y || models[f0 + k]->one_c != models[f0]->one_c) { n = k; break; }
 		vfgs::FrameTable ft{};
 		for (unsigned k = 0; k < n; k++)
 		{
@@ -3026,8 +3114,20 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			ft.src[0][k] = (const uint8_t*)a.Y; ft.src[1][k] = (const uint8_t*)a.U; ft.src[2][k] = (const uint8_t*)a.V;
 			ft.dst[0][k] = (uint8_t*)b.Y; ft.dst[1][k] = (uint8_t*)b.U; ft.dst[2][k] = (uint8_t*)b.V;
 		}
+		ModelRun mr{};
+		if (models)
+		{
+			for (unsigned k = 0; k < n; k++)
+			{
+				vfgs_hip_model* m = const_cast<vfgs_hip_model*>(models[f0 + k]);
+				HIP_TRY(m->guard.use(stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
+				ft.model[k] = m->dev;
+			}
+			mr.one_y = models[f0]->one_y; mr.one_c = models[f0]->one_c;
+			mr.first = models[f0]->rec;
+		}
 		if (int e = run_device(src[f0].Y, src[f0].U, src[f0].V, dst[f0].Y, dst[f0].U, dst[f0].V, width, 0, height, part_y, part_h, stride, cstride,
-		                       n, 0, 0, stream, dg, &ft, seeded ? seeds + f0 : nullptr, sp_shift))
+		                       n, 0, 0, stream, dg, &ft, seeded ? seeds + f0 : nullptr, sp_shift, models ? &mr : nullptr))
 			return e;
 	}
 	return 0;
@@ -3110,6 +3210,128 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
 	dg.out8 = true;
 	dg.stride = dst_stride; dg.cstride = dst_cstride;
 	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), dg, true, 0, 0, true, seeds);
+}
+
+// Models as objects (vfgs_hip.h).  Capture builds the image upload_tables would build for ordinary rows -- same form, same bytes, device-generated
+// slots patched in on the device -- into a buffer the model owns, with the record of per-launch values in front, and leaves the programmed
+// state, its image ring and tables_dirty alone.
+int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream_)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (!out) return fail(41, "vfgs_hip_model_capture: null result pointer");
+	*out = nullptr;
+	if (int e = ensure_init(-1)) return e;
+	State& s = g_states[0];
+	hipStream_t stream = (hipStream_t)stream_;
+	if (s.scale_shift + s.bs < 8 || s.scale_shift + s.bs > 13)   // vfgs_hw.c:170
+		return fail(9, "scale_shift out of range (vfgs_hw.c:170)");
+	if (int e = check_luts(s)) return e;
+	const int slot[3] = {s.plut_slot[0], s.plut_slot[1], s.plut_slot[2]};
+	bool one_y, one_c;
+	image_form(s, false, &one_y, &one_c);
+	const vfgs::ImageLayout L = vfgs::layout_of(s.csubx, s.csuby, one_y, one_c, s.bs == 0);
+	const size_t bytes = (size_t)vfgs::kModelRecordBytes + (size_t)L.bytes;
+	if (int e = fw_flush(s, stream)) return e;
+	// buffers: those of the oldest released model whose readers are done by now (normally long ago), else new ones
+	vfgs_hip_model* m = nullptr;
+	if (g_models_left.size() >= kModelsLeftMax / 2 && g_models_left.front()->cap >= bytes)
+	{
+		m = g_models_left.front();
+		HIP_TRY(m->guard.wait_free());
+		g_models_left.erase(g_models_left.begin());
+	}
+	else
+	{
+		m = new vfgs_hip_model;
+		hipError_t e = hipMalloc((void**)&m->dev, bytes);
+		if (e == hipSuccess) e = hipHostMalloc((void**)&m->host, bytes, hipHostMallocDefault);
+		if (e != hipSuccess) { (void)hipGetLastError(); model_destroy(m); return fail((int)e, "vfgs_hip_model_capture: %zu bytes -> %s", bytes, hipGetErrorString(e)); }
+		m->cap = bytes;
+	}
+	m->bytes = bytes;
+	m->bs = s.bs; m->csubx = s.csubx; m->csuby = s.csuby;
+	m->one_y = one_y; m->one_c = one_c;
+	m->scale_shift = s.scale_shift;
+	m->legal = s.ymin != 0;
+	m->rec = vfgs::ModelRecord{};
+	m->rec.lo2[0] = (uint32_t)(s.ymin << s.bs) * 0x10001u; m->rec.hi2[0] = (uint32_t)(s.ymax << s.bs) * 0x10001u;
+	m->rec.lo2[1] = (uint32_t)(s.cmin << s.bs) * 0x10001u; m->rec.hi2[1] = (uint32_t)(s.cmax << s.bs) * 0x10001u;
+	m->rec.pk_shift = s.scale_shift;
+	memcpy(m->host, &m->rec, sizeof m->rec);
+	build_tables(s, m->host + vfgs::kModelRecordBytes, L, one_y, one_c, slot);
+	hipError_t e = hipMemcpyAsync(m->dev, m->host, bytes, hipMemcpyHostToDevice, stream);
+	int fwe = 0;
+	if (e == hipSuccess && (s.dev_origin[0] | s.dev_origin[1]))
+	{
+		// device-generated slots never visit the host: copy them bank -> image on the device (upload_tables)
+		fwe = fw_bank_stream(s, stream);
+		if (!fwe)
+			e = vfgs::launch_fw_patch(m->dev + vfgs::kModelRecordBytes, s.dev_bank, s.dev_origin[0], s.dev_origin[1], s.csubx, s.csuby, one_y, one_c,
+			                          slot[0], slot[1], slot[2], s.bs == 0, stream);
+	}
+	if (e == hipSuccess && !fwe) e = m->guard.uploaded(stream);
+	if (e != hipSuccess || fwe)
+	{
+		(void)hipStreamSynchronize(stream);     // (whatever was queued on the buffers is done before they go)
+		model_destroy(m);
+		return fwe ? fwe : fail((int)e, "vfgs_hip_model_capture: %s", hipGetErrorString(e));
+	}
+	g_models.push_back(m);
+	*out = m;
+	return 0;
+}
+
+void vfgs_hip_model_release(vfgs_hip_model* m)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	auto it = std::find(g_models.begin(), g_models.end(), m);
+	if (it == g_models.end()) return;      // NULL, released before, or gone with vfgs_hip_shutdown
+	g_models.erase(it);
+	if (g_states[0].inited) (void)ensure_init(-1);
+	(void)m->guard.leave();                // an event behind everything queued so far on every stream that read the image
+	g_models_left.push_back(m);
+	if (g_models_left.size() > kModelsLeftMax)
+	{
+		vfgs_hip_model* old = g_models_left.front();
+		g_models_left.erase(g_models_left.begin());
+		(void)old->guard.wait_free();      // (normally long complete)
+		model_destroy(old);
+	}
+}
+
+int vfgs_hip_model_info(const vfgs_hip_model* m, int out[8])
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (!out) return fail(41, "vfgs_hip_model_info: null result");
+	if (!model_live(m)) return fail(41, "vfgs_hip_model_info: %s", m ? "the model was released" : "null model");
+	const int v[8] = {8 + m->bs, m->csubx, m->csuby, m->one_y, m->one_c, m->scale_shift, m->legal, (int)m->bytes};
+	memcpy(out, v, sizeof v);
+	return 0;
+}
+
+int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const vfgs_hip_model* const* models,
+                                             const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                             unsigned cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	if (!models) return fail(41, "frame list with models: null list of models for %u frames", nframes);
+	for (unsigned f = 0; f < nframes; f++)
+	{
+		const vfgs_hip_model* m = models[f];
+		if (!model_live(m)) return fail(41, "frame list with models: the model of frame %u is %s", f, m ? "not a live model (released?)" : "null");
+		if (m->bs != s.bs || m->csubx != s.csubx || m->csuby != s.csuby)
+			return fail(41, "frame list with models: the model of frame %u was captured at depth %d, chroma subsampling %d,%d; programmed: depth %d, %d,%d", f,
+			            8 + m->bs, m->csubx, m->csuby, 8 + s.bs, s.csubx, s.csuby);
+	}
+	if (width > (unsigned)vfgs::kTileBlocks * 16)
+		return fail(41, "frame list with models: width %u, rows of more than %d samples are walked in parts and have no kernel with a model per frame", width, vfgs::kTileBlocks * 16);
+	if (mix_active())
+		return fail(41, "frame list with models: a chroma mix is active; the mix is one per launch, not one per model (clear it, or grain such pictures with the calls that honour it)");
+	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom(), true, 0, 0, seeds != nullptr, seeds, -1, models);
 }
 
 // Semi-planar frames (vfgs_hip.h): a luma plane and ONE plane of interleaved Cb/Cr pairs per frame.  What this call alone refuses is

@@ -683,7 +683,11 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     SP = 2 (luma planes of grain_p2sp_kernel / grain_p2sp8_kernel: a PLANAR source, a semi-planar destination): the source is read as it lies,
 //     low-aligned -- nothing is shifted down -- the results go up or are narrowed as above, and the destination has a geometry of its own
 //     (dpitch, drowbytes) at either container size.
-template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0>
+//   * MODELS (grain_ml_kernel: a model per frame): the table image, the clip bounds and the packed form's shift are those of the
+//     workgroup's FRAME -- FrameTable::model[f] points at a ModelRecord with the image behind it -- fetched with scalar loads (the pointer from
+//     the kernel arguments, the record through it) in front of the image loads; everything they feed stays wave-uniform.  Without the flag
+//     the values are the launch's, from KernelArgs, and nothing of this exists.
+template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0, bool MODELS = false>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
 {
@@ -711,6 +715,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
+	static_assert(!MODELS || (!OUT8 && !WIDE && !PERSIST && !MIX && !SP), "a model per frame: the plain planar walk, one task per workgroup");
 	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
@@ -753,9 +758,22 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	constexpr int STEP = kWavesPerWG * 64 * 16;
 	constexpr int NIT = (IMG_BYTES + STEP - 1) / STEP;
 	u32x4 tmp[NIT];
+	// MODELS: my frame's model -- its record (constant address space: scalar loads) and the image behind it
+	const uint8_t* mtables = nullptr;
+	uint32_t mlo2 = 0, mhi2 = 0;
+	int mpk_shift = 0;
+	if constexpr (MODELS)
+	{
+		typedef const uint32_t __attribute__((address_space(4)))* crec_t;
+		const uint8_t* const mp = ft.model[f];
+		const crec_t rec = (crec_t)(uintptr_t)mp;
+		mlo2 = rec[pt]; mhi2 = rec[2 + pt];
+		mpk_shift = (int)rec[4];
+		mtables = mp + kModelRecordBytes;
+	}
 	if (!PERSIST || first_task)
 	{
-		const __amdgpu_buffer_rsrc_t irs = make_rsrc(a.tables + img_off, IMG_BYTES);
+		const __amdgpu_buffer_rsrc_t irs = make_rsrc((MODELS ? mtables : a.tables) + img_off, IMG_BYTES);
 #pragma unroll
 		for (int it = 0; it < NIT; it++)      // threads beyond the image re-read (and re-write) its last unit
 			tmp[it] = __builtin_amdgcn_raw_buffer_load_b128(irs, min((uint32_t)(threadIdx.x * 16 + it * STEP), (uint32_t)(IMG_BYTES - 16)), 0, 0);
@@ -888,8 +906,8 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 
 	// ---- per lane constants ------------------------------------------------------------------------------------------
 	const uint32_t lutb = lut_off * 0x10001u;
-	const uint32_t lo2 = a.lo2[pt], hi2 = a.hi2[pt];
-	const bool first = M::PAIR && (lane & 1);                              // PAIR: odd lane positions hold the first half of a block
+	const uint32_t lo2 = MODELS ? mlo2 : a.lo2[pt], hi2 = MODELS ? mhi2 : a.hi2[pt];
+	const bool first = M::PAIR && (lane & 1);                             // PAIR: odd lane positions hold the first half of a block
 	const uint32_t pairoff = M::PAIR ? (first ? 0u : 8u * SB) : 0u;
 	const uint32_t idx0 = (M::PAIR ? (uint32_t)(lane + 1) >> 1 : (uint32_t)lane * LPB) * 4;   // byte offset of my first entry in position 0 of a part
 	const int cl = M::PAIR ? lane - 1 - (lane & 1) : lane * LPB - 1;       // PAIR: left unit of my lane pair; else: block of run 0 (both for position 0)
@@ -980,13 +998,13 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 					{
 #pragma unroll
 						for (int rr = 0; rr < NR; rr++) up.pa[rr] = *(const uint32_t*)(pe + PT_UP + (p * BPS + rr) * 4) + pairoff;
-						grain_unit<DEPTH, BW, true, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, wc_, wu_, edge_on, first, lo2, hi2, a.pk_shift, t);
+						grain_unit<DEPTH, BW, true, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, wc_, wu_, edge_on, first, lo2, hi2, MODELS ? mpk_shift : a.pk_shift, t);
 					}
 					else
 					{
 #pragma unroll
 						for (int rr = 0; rr < NR; rr++) up.pa[rr] = 0u;
-						grain_unit<DEPTH, BW, false, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, 0, 0, edge_on, first, lo2, hi2, a.pk_shift, t);
+						grain_unit<DEPTH, BW, false, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, 0, 0, edge_on, first, lo2, hi2, MODELS ? mpk_shift : a.pk_shift, t);
 					}
 				}
 				uint32_t o[DW];
@@ -1104,9 +1122,9 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 #pragma unroll
 					for (int rr = 0; rr < NR; rr++) up.pa[rr] = OV ? *(const uint32_t*)(pe + PT_UP + (u * BPS + rr) * 4) + pairoff : 0u;
 					if constexpr (MIX)
-						grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG, true>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, a.pk_shift, ti);
+						grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG, true>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, MODELS ? mpk_shift : a.pk_shift, ti);
 					else
-						grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, a.pk_shift, t);
+						grain_unit<DEPTH, BW, OV, ONE, ONE && SUBX == 2, NEG>(lds, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, first, lo2, hi2, MODELS ? mpk_shift : a.pk_shift, t);
 				}
 				uint32_t o[DW];
 				results(t, o);
@@ -1243,6 +1261,38 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, WIDE ? 0 : 1, OUT8, WIDE, false>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
 		else
 			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, 0, OUT8, WIDE, false>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+	}
+}
+
+// A MODEL PER FRAME (KernelArgs::models_kernel; vfgs_hip_add_grain_frame_list_models_dev): listed frames whose models share
+// the form (ONEY, ONEC) of their table images and nothing else.  The grid, the workgroup numbering, the two frame fronts, the narrow chroma
+// rows, the launch bounds and the LDS allocation of grain_rw_kernel<DEPTH, CSUBX, CSUBY, false, ONEY, ONEC, false, false>; a workgroup
+// stages ITS frame's image and clips with ITS frame's bounds (run_plane_rw MODELS).  No persistent luma workgroups: a workgroup that keeps
+// one staged image for several tasks would need them to be tasks of one model.
+template <int DEPTH, int CSUBX, int CSUBY, bool ONEY, bool ONEC>
+__global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, ONEC, false>())) void grain_ml_kernel(const KernelArgs a, const FrameTable ft)
+{
+	constexpr ImageLayout L = image_layout(CSUBX, CSUBY, ONEY, ONEC, DEPTH == 8);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[lds_allocation(DEPTH > 8, ONEY, ONEC, false, L.lds_bytes + kParamBytes)];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	if (r < a.pd[0].wgs)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, 0, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+	{
+		r -= a.pd[0].wgs;
+		const int comp = 1 + (r >= a.pd[1].wgs);
+		if (comp == 2) r -= a.pd[1].wgs;
+		if (CSUBX == 2 && a.pd[1].rw_segs == 2 && ring_depth<DEPTH, ONEC>() >= 2)
+			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, 2, false, false, false, false, 0, true>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+		else if (CSUBX == 2 && a.pd[1].rw_segs == 1)
+			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, 1, false, false, false, false, 0, true>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+		else
+			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, 0, false, false, false, false, 0, true>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
 	}
 }
 
@@ -1957,9 +2007,32 @@ static hipError_t launch_sp_mix(const KernelArgs& a, const FrameTable& ft, int g
 	return hipGetLastError();
 }
 
+template <int DEPTH, int CSUBX, int CSUBY>
+static hipError_t launch_ml(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	if (oney && onec) hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, true, true>), g, b, 0, stream, a, ft);
+	else if (oney) hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, true, false>), g, b, 0, stream, a, ft);
+	else if (onec) hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, false, true>), g, b, 0, stream, a, ft);
+	else hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, false, false>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
 template <int D>
 static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
 {
+	if (a.models_kernel)
+	{
+		// a model per frame: listed whole planar frames, rows of one parameter table, no mix, every frame with a model image (the host refuses everything else)
+		if (a.models_kernel != 1 || a.sp_kernel || a.mix_kernel || out8 || wide || persist || !a.listed) return hipErrorInvalidValue;
+		for (int f = 0; f < a.nframes; f++)
+			if (!ft.model[f] || ((uintptr_t)ft.model[f] & 15)) return hipErrorInvalidValue;
+		if (csubx == 2 && csuby == 2) return launch_ml<D, 2, 2>(a, ft, oney, onec, grid, stream);
+		if (csubx == 2 && csuby == 1) return launch_ml<D, 2, 1>(a, ft, oney, onec, grid, stream);
+		if (csubx == 1 && csuby == 1) return launch_ml<D, 1, 1>(a, ft, oney, onec, grid, stream);
+		if (csubx == 1 && csuby == 2) return launch_ml<D, 1, 2>(a, ft, oney, onec, grid, stream);
+		return hipErrorInvalidValue;
+	}
 	if (a.sp_kernel)
 	{
 		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table (the host refuses everything else)

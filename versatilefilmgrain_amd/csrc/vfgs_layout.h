@@ -252,12 +252,27 @@ struct PlaneDesc {
 // Frames of a batch that do NOT lie at a constant pitch (a decoder's pool of separately allocated frames, vfgs_hip_add_grain_frame_list_*):
 // their plane pointers travel in the kernel arguments themselves -- no device table to upload and keep alive, no copy on the
 // stream in front of the launch -- and a workgroup fetches its frame's pointers with one scalar load.  kListFrames frames per
-// launch (longer lists: several launches); 2 x 3 x 8 x kListFrames bytes of the 4 KB argument segment.
+// launch (longer lists: several launches); (2 x 3 + 1) x 8 x kListFrames bytes of the 4 KB argument segment.
 constexpr int kListFrames = 32;
 struct FrameTable {
 	const uint8_t* src[3][kListFrames];   // [component][frame of the launch]: first line of the stripe
 	uint8_t* dst[3][kListFrames];
+	// A model per frame (KernelArgs::models_kernel, vfgs_hip_add_grain_frame_list_models_dev): the device image of frame f's model, a
+	// ModelRecord followed by the table image (image_layout).  Behind the plane pointers: the kernels of before never look this far, and
+	// the table is the LAST kernel argument, so nothing they load has moved.
+	const uint8_t* model[kListFrames];
 };
+
+// What a captured model (vfgs_hip_model_capture) keeps in front of its table image: the values that are one per launch in KernelArgs
+// for every other call -- lo2 / hi2 per plane type and pk_shift, exactly as KernelArgs holds them.  A workgroup of grain_ml_kernel reads
+// its frame's record with scalar loads before it issues the loads of the image.  32 bytes: the image behind it stays 16-byte aligned.
+struct ModelRecord {
+	uint32_t lo2[2], hi2[2];
+	int32_t pk_shift;
+	uint32_t reserved[3];
+};
+constexpr int kModelRecordBytes = 32;
+static_assert(sizeof(ModelRecord) == kModelRecordBytes, "the table image begins 32 bytes behind the record");
 
 // One launch = nframes x (luma workgroups + 2 x chroma workgroups); workgroups are numbered in memory
 // order (frame, plane, block row group, split, column group) and are NOT persistent: the hardware
@@ -268,6 +283,11 @@ struct KernelArgs {
 	PlaneDesc pd[2];
 	const uint32_t* stream;   // LFSR bit stream cache (device), bit m = word[m>>5] >> (m&31)
 	uint32_t stream_bytes;
+	// 1: grain_ml_kernel serves the launch (listed frames; FrameTable::model[f] is frame f's model image and `tables` below frame 0's table
+	// image).  The field sits HERE, in the four bytes that used to be padding in front of the pointer below: the frame table is the kernel
+	// argument BEHIND this structure, so a field appended at the end would move every plane pointer the kernels of before load (the
+	// static_assert below the structure holds its size).
+	int models_kernel;
 	const uint8_t* tables;    // device image (image_layout)
 	uint32_t cur_bit0;        // stream bit of the register of block 0, first block row of the stripe, frame 0
 	uint32_t up_bit0;         // same for the "upper" register of that first block row
@@ -294,5 +314,6 @@ struct KernelArgs {
 	                          //    component's bytes of its row (the row holds twice as many); pd[0].dpitch / drowbytes: the destination's luma row
 	uint32_t sp_shift2;       // ... 16-bit containers: the samples sit this many bits up (P010: 6, P012: 4), in both halves of the dword (a packed 16-bit shift each way)
 };
+static_assert(sizeof(KernelArgs) == 304, "the frame table follows KernelArgs in the kernel arguments: a new size moves what every kernel loads from it");
 
 }  // namespace vfgs

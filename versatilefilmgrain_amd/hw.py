@@ -121,6 +121,11 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_add_grain_sp_frame_list_copy8_dev.argtypes = [spf, spf, sp, u, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_to_sp_dev.argtypes = [fp, spf, sp, u, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_to_sp8_dev.argtypes = [fp, spf, sp, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_model_capture.argtypes = [C.POINTER(vp), vp]
+    lib.vfgs_hip_model_release.argtypes = [vp]
+    lib.vfgs_hip_model_release.restype = None
+    lib.vfgs_hip_model_info.argtypes = [vp, C.POINTER(i)]
+    lib.vfgs_hip_add_grain_frame_list_models_dev.argtypes = [fp, fp, C.POINTER(vp), sp, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -190,6 +195,7 @@ EXPORTS = [
     "vfgs_hip_add_grain_frame_list_to_sp_dev", "vfgs_hip_add_grain_frame_list_to_sp8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
+    "vfgs_hip_model_capture", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
 ]
 
 
@@ -369,6 +375,34 @@ class VfgsHip:
         assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
         self._ck(self.lib.vfgs_hip_add_grain_frame_list_to_sp8_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, cstride,
                                                                    dst_stride, dst_uv_stride, stream))
+
+    # ---- models as device objects (include/vfgs_hip.h)
+    def model_capture(self, stream=0):
+        """Snapshot of what is programmed now -- patterns (device-generated ones included), LUTs, scale shift, range, at the programmed depth
+        and chroma format -- as a device-resident model; returns its handle (an integer).  Asynchronous on `stream`; nothing else changes."""
+        m = C.c_void_p()
+        self._ck(self.lib.vfgs_hip_model_capture(C.byref(m), stream))
+        return m.value
+
+    def model_release(self, m):
+        """Release a model (None: no-op); allowed as soon as the call that used it has returned."""
+        self.lib.vfgs_hip_model_release(m)
+
+    def model_info(self, m):
+        out = (C.c_int * 8)()
+        self._ck(self.lib.vfgs_hip_model_info(m, out))
+        return dict(zip(("depth", "csubx", "csuby", "one_y", "one_c", "scale_shift", "legal_range", "device_bytes"), out))
+
+    def add_grain_frame_list_models_dev(self, src, dst, models, seeds, width, height, stride, cstride, stream=0):
+        """The list call with a model per picture: frame f is grained as if models[f]'s state were programmed (and, with seeds,
+        vfgs_set_seed(seeds[f]) called) in front of it; one launch per run of at most 32 frames whose models share the form of their images.
+        dst is src (or None): in place.  The programmed state is unchanged.  VfgsHipError 41: a null / released model, a model of another
+        depth or chroma format, width > 8192, an active chroma mix."""
+        s = self.frame_list(src)
+        d = s if (dst is None or dst is src) else self.frame_list(dst)
+        assert len(s) == len(d) == len(models) and (seeds is None or len(seeds) == len(s))
+        arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_models_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, cstride, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
