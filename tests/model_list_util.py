@@ -10,11 +10,24 @@ and the ground truth is the oracle run as that loop:
   model's program in the banks are harmless; what a program does not set at all would not be -- the SEI programs never set the range --
   so a model program here always begins with the power-on range (model_records).
 
-A model is named by its trace in tests/golden/traces ("name"), at depth 12 by "name@depth12" (test_gpu_depth12.records12)."""
+A model is named by its trace in tests/golden/traces ("name"), at depth 12 by "name@depth12" (test_gpu_depth12.records12), or by the name of
+a generated program (tests/model_programs.py)."""
+import model_programs as MP
 import vfgs_testlib as T
+
+_names = None
+
+
+def _generated():
+    global _names
+    if _names is None:
+        _names = frozenset(MP.names())
+    return _names
 
 
 def model_records(name):
+    if name in _generated():
+        return MP.program(name)         # (a generated program sets everything, the range included)
     if name.endswith("@depth12"):
         import test_gpu_depth12 as D
         rec = D.records12(name[:-len("@depth12")])

@@ -1,0 +1,233 @@
+"""GPU (MI355X): the generated programs of tests/model_programs.py captured as models (vfgs_hip_model_capture) and used a model per picture
+(vfgs_hip_add_grain_frame_list_models_dev, grain_ml_kernel), against the oracle run as the contract's loop (tests/model_list_util.py), bit
+for bit: every sample of every plane, padding included, and the four seed registers.
+
+Capture chooses the form and builds the image on its own, stores the scale shift of the packed 16-bit form and the clip bounds per model,
+and the kernel reads them from the frame's record.  tests/test_gpu_model_list.py captures firmware traces only: no model with slot 8, with
+Cb and Cr on different slots, with a -128, at the packed 16-bit limit, with a scale_shift other than 4 / 5, or programmed by a shuffled
+sequence.  Here every generated program is a model, and the models whose per-model values differ most share launches.
+
+Frames are MP.content of the frame's own model (in-range and garbage content in turn: garbage in 16-bit containers lies mostly above the
+range, where the clip hides the grain), every frame an allocation of its own, listed out of address order.  Shapes: 328 x 56, the
+generator's own (21 blocks, 3.5 block rows), and 352 x 56 as well at 8 bit 4:2:0 / 4:2:2 (22 blocks: the aligned rows)."""
+import pytest
+
+import chroma_mix_util as X
+import model_list_util as U
+import model_programs as MP
+import vfgs_testlib as T
+from gpu_util import DevFrame, stream_ptr
+from test_gpu_model_list import Models, fresh_seeds, run
+
+pytestmark = pytest.mark.gpu
+
+W, H = 328, 56
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from versatilefilmgrain_amd import hw
+    h = hw.VfgsHip(device=0)
+    yield h
+    h.lib.vfgs_hip_reset_state()
+
+
+def widths(depth, fmt):
+    return (W, 352) if depth == 8 and fmt in ("420", "422") else (W,)
+
+
+def frames_for(ms, pick, w, tag):
+    """one frame per entry of pick, of that entry's own model's content; the variants alternate along the list"""
+    turn = [(i + tag) % 2 for i in range(len(pick))]
+    pools, out = {}, []
+    for k, v in zip(pick, turn):
+        if (k, v) not in pools:
+            pools[k, v] = MP.content(ms.names[k], w, H, sum(1 for kk, vv in zip(pick, turn) if (kk, vv) == (k, v)), MP.VARIANTS[v])
+        out.append(pools[k, v].pop(0))
+    return out
+
+
+def state_of(rec):
+    st = T.StateModel()
+    T.replay(st, rec)
+    return st
+
+
+def check_models(ms):
+    """what model_info reports is what was programmed: the form the documented rule gives, the stored scale shift, the range"""
+    for name, rec, info in zip(ms.names, ms.recs, ms.info):
+        st = state_of(rec)
+        assert (bool(info["one_y"]), bool(info["one_c"])) == MP.expected_form(rec), (name, info)
+        assert (info["depth"], info["csubx"], info["csuby"]) == (8 + st.bs, st.subx, st.suby), (name, info)
+        assert info["scale_shift"] == st.shift and info["legal_range"] == int(X.legal_range(rec)), (name, info, st.shift)
+
+
+def kernel_of(ms, k):
+    oy, oc = ms.forms[k]
+    b = lambda v: "true" if v else "false"
+    return f"grain_ml_kernel<{ms.depth},{ms.sx},{ms.sy},{b(oy)},{b(oc)}>"
+
+
+def run_list(hip, ms, pick, w, seeded, tag, out_of_place=False):
+    """the list through the call against the contract's loop (test_gpu_model_list.run compares everything); -> the device frames"""
+    frames = frames_for(ms, pick, w, tag)
+    ora = None
+    if not seeded:
+        # one seed sequence: it begins at registers both sides know (an earlier list has moved the library's)
+        ora = U.oracle_programmed(ms.recs[-1])
+        hip.set_seed(0xC0FFEE + tag)
+        ora.set_seed(0xC0FFEE + tag)
+    n0 = U.launches(hip)
+    dev, _ = run(hip, ms, pick, frames, fresh_seeds(len(pick), tag) if seeded else None, ora=ora, shuffle=tag, out_of_place=out_of_place)
+    info = hip.last_launch_info()
+    runs = U.runs_of(ms.forms, pick)
+    assert info["launches"] - n0 == len(runs) and info["nframes"] == runs[-1] and info["listed"] == 1, (info, runs)
+    assert info["kernel"] == kernel_of(ms, pick[-1]) and info["in_place"] == (0 if out_of_place else 1), info
+    assert hip.seeded_stream_stats()["last_launch_used_it"] == seeded
+    return dev
+
+
+def in_one_launch(hip, names, pick):
+    """models of one form in one launch, with a seed sequence and with a seed per picture, at every width of the format"""
+    ms = Models(hip, names)
+    try:
+        check_models(ms)
+        assert len(set(ms.forms)) == 1, ms.forms
+        _, depth, fmt, _ = MP.parse(names[0])
+        for w in widths(depth, fmt):
+            for seeded in (False, True):
+                n0 = U.launches(hip)
+                run_list(hip, ms, pick, w, seeded, 3 + int(seeded))
+                info = hip.last_launch_info()
+                assert info["launches"] - n0 == 1 and info["nframes"] == len(pick), info
+        return ms.info
+    finally:
+        ms.release()
+
+
+# ---- every program is a model ----------------------------------------------------------------------------------------------------
+
+GROUPS = [(d, f) for d in MP.DEPTHS for f in MP.FORMATS]
+
+
+def test_the_groups_hold_every_program():
+    assert len(GROUPS) == 12 and sorted(n for d, f in GROUPS for n in MP.names(depth=d, fmt=f)) == sorted(MP.names()) and len(MP.names()) == 225
+
+
+@pytest.mark.parametrize("depth, fmt", GROUPS)
+def test_every_program_is_a_model(hip, depth, fmt):
+    """every program of the group captured; a frame per model in two lists -- ordered by form (few launches, each with many different
+    models) and shuffled (the form changes inside the list) -- each with one seed sequence and with a seed per picture"""
+    names = MP.names(depth=depth, fmt=fmt)
+    ms = Models(hip, names)
+    try:
+        check_models(ms)
+        by_form = sorted(range(len(names)), key=lambda k: ms.forms[k])
+        shuffled = MP.Rng(f"model list/{depth}/{fmt}").shuffle(range(len(names)))
+        assert len(U.runs_of(ms.forms, by_form)) == len(set(ms.forms)) == 4 and len(U.runs_of(ms.forms, shuffled)) >= 8
+        oop = GROUPS.index((depth, fmt)) % 2 == 1
+        for seeded in (False, True):
+            run_list(hip, ms, by_form, W, seeded, 1)
+            run_list(hip, ms, shuffled, W, seeded, 2, out_of_place=oop)
+        for w in widths(depth, fmt)[1:]:
+            run_list(hip, ms, by_form, w, True, 5, out_of_place=oop)
+            run_list(hip, ms, shuffled, w, False, 6)
+    finally:
+        ms.release()
+
+
+# ---- the packed 16-bit limit per model, 8 bit --------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", ["420", "422"])
+@pytest.mark.parametrize("variants, form", [(("s5", "s7"), (True, False)), (("s5y", "s7y"), (False, True)), (("s2", "s2y", "one_same_slot"), (True, True))],
+                         ids=["s5_s7", "s5y_s7y", "s2_s2y_one_same_slot"])
+def test_the_packed_16_bit_limit_per_model(hip, variants, form, fmt):
+    """models of one form whose components sit at (and one over) the limit of DIFFERENT scale shifts alternate in one launch: a workgroup
+    that took frame 0's pk_shift would be wrong on every other frame"""
+    names = [f"one_same_slot_8_{fmt}" if v == "one_same_slot" else f"pk16_split_8_{fmt}_{v}" for v in variants]
+    assert all(MP.expected_form(MP.program(n)) == form for n in names)
+    n = len(names)
+    info = in_one_launch(hip, names, [i % n for i in range(2 * n + 1)])
+    assert len({i["scale_shift"] for i in info}) == 2, info
+
+
+# ---- slots per model in one launch -----------------------------------------------------------------------------------------------
+
+SLOT_CLASSES = ["slot8_luma", "slot8_cb", "slot8_chroma", "one_cb_cr_differ", "one_same_slot", "m128_unselected", "m128_outside_window"]
+
+
+@pytest.mark.parametrize("depth, fmt", [(10, "420"), (12, "444")])
+def test_slots_per_model_in_one_launch(hip, depth, fmt):
+    """all one-pattern, each with slots of its own (slot 8 for luma, for Cb, for both chroma components; Cb and Cr apart; a -128 next to the
+    selected slot): A B C ... A in one launch"""
+    names = [f"{c}_{depth}_{fmt}" for c in SLOT_CLASSES if MP.names(c, depth, fmt)]
+    assert len(names) == (7 if fmt != "444" else 6)
+    assert all(MP.expected_form(MP.program(n)) == (True, True) for n in names)
+    in_one_launch(hip, names, list(range(len(names))) + [0])
+
+
+# ---- a shuffled program captures its twin's model ----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["shuffled_0_8_420", "shuffled_1_10_444", "shuffled_2_12_422", "shuffled_2_8_440"])
+def test_a_shuffled_program_captures_its_twins_model(hip, name):
+    """the same frames with the same seeds through both models in one list: byte-identical, and the oracle's"""
+    ms = Models(hip, [name, MP.twin_of(name)])
+    try:
+        check_models(ms)
+        a, b = ms.info
+        assert a == b
+        n = 3
+        half = MP.content(name, W, H, n, "in_range")
+        frames = half + [f.copy() for f in half]
+        seeds = fresh_seeds(n, 9) * 2
+        pick = [0] * n + [1] * n
+        n0 = U.launches(hip)
+        dev, _ = run(hip, ms, pick, frames, seeds, shuffle=7)
+        assert hip.last_launch_info()["launches"] - n0 == 1
+        got = [d.download() for d in dev]
+        for i in range(n):
+            assert got[i].equal_all(got[i + n]), i
+    finally:
+        ms.release()
+
+
+# ---- capture is a snapshot ---------------------------------------------------------------------------------------------------------
+
+def test_capture_is_a_snapshot_of_the_form(hip):
+    """after the capture a -128 goes into the selected Cb slot through the setter: the PROGRAMMED state now has general-form chroma, the
+    model grains as captured (one-pattern), and a plain frame call afterwards runs the general chroma form"""
+    name = "one_cb_cr_differ_10_420"
+    ms = Models(hip, [name])
+    try:
+        check_models(ms)
+        rec = ms.recs[0]
+        assert ms.forms[0] == (1, 1)
+        st = state_of(rec)
+        cb = st.plut[1][0] >> 4
+        dirty = MP._spec(name).chroma[cb].copy()
+        assert not (dirty == -128).any()
+        dirty[int(MP.copied_offsets("420")[5])] = -128
+        step = [(T.OP_CHROMA_PATTERN, cb, 0, dirty.tobytes())]
+        T.replay(hip, step)
+        assert MP.expected_form(rec + step) == (True, False)
+        pick = [0, 0, 0]
+        frames = MP.content(name, W, H, 4, "in_range")
+        n0 = U.launches(hip)
+        _, ora = run(hip, ms, pick, frames[:3], None, shuffle=8)
+        info = hip.last_launch_info()
+        assert info["launches"] - n0 == 1 and info["kernel"] == kernel_of(ms, 0) and (info["one_y"], info["one_c"]) == (1, 1), info
+        assert hip.model_info(ms.handles[0]) == ms.info[0]
+        # a plain frame call: what is programmed now, the registers the list left
+        T.replay(ora, step)
+        f = frames[3]
+        want = f.copy()
+        ora.add_grain_frame(want)
+        d = DevFrame(f)
+        hip.add_grain_frame_dev(*d.ptrs(), f.width, f.height, f.stride, f.cstride, stream_ptr())
+        info = hip.last_launch_info()
+        assert (info["one_y"], info["one_c"]) == (1, 0), info
+        assert d.download().equal_all(want) and hip.seed_state() == ora.seed_state()
+    finally:
+        ms.release()

@@ -6,6 +6,7 @@ the firmware traces the rest of the suite is programmed from never reach a gener
 different slots, a -128, a scale LUT at the packed 16-bit limit of ONE component, or scale_shift 7.  Every test here compares whole
 buffers (row padding included) and the four seed registers after every call, and asserts the form and depth the launch reports
 (last_launch_info) against MP.expected_form -- a class that silently ran the general form would prove nothing.
+The surface kernels (semi-planar frames) and the model-list kernel: tests/test_gpu_model_programs_surfaces.py, tests/test_gpu_model_list_programs.py.
 
 Shapes: 328 x 56 (21 blocks: the shifted 8-bit kernels at 4:2:0 / 4:2:2, the last block half in the padding, 3.5 block rows),
 352 x 56 (22 blocks: the aligned 8-bit kernels), 8208 x 40 (rows walked in two parts).
