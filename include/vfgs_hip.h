@@ -269,7 +269,7 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
  * cases the planar calls refuse with error 38 on D(src); like every device-pointer call this one runs on the primary device, also while
  * several devices are set (vfgs_hip_init_devices), and honours the mix there.  An empty list is no call at all.
  * Out of scope, on purpose: stripe / part forms, host-memory entry points, 4:4:4 semi-planar, persistent luma workgroups (the narrowed
- * 8-bit destination is the _copy8 call below). */
+ * 8-bit destination is the _copy8 call below; a model per picture is vfgs_hip_add_grain_sp_frame_list_models_dev, further down). */
 typedef struct vfgs_hip_sp_frame { void* Y; void* UV; } vfgs_hip_sp_frame;
 int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                          const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
@@ -397,13 +397,43 @@ int  vfgs_hip_model_info(const vfgs_hip_model* m, int out[8]);
  * capture, and that a null `seeds` selects the single seed sequence (no error 39) -- and, error 41 with a message that names the cause:
  * models == NULL, or a NULL or released entry; a model captured at another depth or chroma format than the programmed one; width > 8192
  * (rows walked in parts); an active chroma mix ("chroma mix" in the message).  An empty list is no call at all.
- * Out of scope, on purpose: the mix per model, the narrowed 8-bit destination, stripe / part forms, semi-planar surfaces, host-memory
- * entry points, widths above 8192, persistent luma workgroups (1080p general-form luma runs without them here). */
+ * Out of scope, on purpose: the mix per model, the narrowed 8-bit destination, stripe / part forms, host-memory entry points, widths
+ * above 8192, persistent luma workgroups (1080p general-form luma runs without them here).  Semi-planar surfaces have the call below. */
 int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
                                              const vfgs_hip_model* const* models,     /* nframes entries */
                                              const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
                                              unsigned nframes, unsigned width, unsigned height,
                                              unsigned stride, unsigned cstride, void* stream);
+
+/* ... on SEMI-PLANAR surfaces: what a player with a hardware decoder has -- NV12 / NV16 / P010 / P210 / P012 surfaces, and a grain model
+ * with each of them.  src / dst / seeds / the geometry / sample_shift and the in-place rule exactly as in
+ * vfgs_hip_add_grain_sp_frame_list_dev; models exactly as in vfgs_hip_add_grain_frame_list_models_dev: the same handles, captured from
+ * planar or semi-planar programming alike (capture knows no frame layout).  The containers written, the bytes left alone and the four seed
+ * registers afterwards are those of
+ *     for f in list order:
+ *         program the state models[f] was captured from;
+ *         if (seeds) vfgs_set_seed(seeds[f]);
+ *         vfgs_hip_add_grain_sp_frame_list_dev(&src[f], &dst[f], NULL, 1, ...)      (no chroma mix active)
+ * and the library's own programmed state is UNCHANGED by the call.
+ * Launches: one per run of at most 32 consecutive frames whose models share (one_y, one_c); a change of form starts a new launch, a change
+ * of anything else does not.  vfgs_hip_last_launch_info(): listed = 1, kernel grain_spml_kernel<depth,csuby,oney,onec>, `launches` counts
+ * every run.  No copy is queued in front of a launch on account of models.  In place is ONE launch: there is no mix, so no luma hazard.
+ * Inside an overlap region the call alternates over the two internal streams; it runs on the primary device.
+ * Refused before anything changes (a refused call does not reseed): everything vfgs_hip_add_grain_sp_frame_list_dev refuses, with its
+ * codes (18 a null list or plane, planes that share bytes -- a UV plane that overlaps another frame's Y included; 7; 5 / 6 / 8 geometry);
+ * error 40 for csubx != 2, a bad sample_shift, width > 8192; the scale shift that counts is each model's, checked at capture; error 41 with
+ * a message that names the cause: models == NULL, a NULL or released entry, a model captured at another depth or chroma format than the
+ * programmed one, an active chroma mix ("chroma mix" in the message).  Where several apply: the list checks, then 40, then 41.  An empty
+ * list is no call at all.
+ * Out of scope, on purpose: the mix per model, the narrowed 8-bit destination, a planar source, stripe / part forms, host-memory entry
+ * points, 4:4:4, widths above 8192. */
+int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
+                                                const vfgs_hip_model* const* models,   /* nframes entries, host memory */
+                                                const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
+                                                unsigned nframes, unsigned width, unsigned height,
+                                                unsigned stride, unsigned uv_stride,   /* containers */
+                                                unsigned sample_shift,                 /* 0, or 16 - depth */
+                                                void* stream);
 
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -1503,7 +1504,7 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
                const vfgs::FrameTable* list = nullptr,     // list: the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
                const uint32_t* seeds = nullptr,            // seeds: frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
                const int sp_shift = -1,                    // >= 0: semi-planar frames (sU == sV, dU == dV: the UV plane, cstride its row in containers), samples that many bits up
-               const ModelRun* mr = nullptr)               // a model per frame (run_frame_list_models): list->model[] holds their images, the programmed state's image stays out of it
+               const ModelRun* mr = nullptr)               // a model per frame (run_frame_list with models; with sp_shift >= 0: on semi-planar frames): list->model[] holds their images, the programmed state's image stays out of it
 {
 	State& s = S();
 	if (list && nframes > (unsigned)vfgs::kListFrames) return fail(19, "internal: a listed launch holds at most %d frames", vfgs::kListFrames);
@@ -1537,8 +1538,8 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (p2sp && (sp || !list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
-	if (mr && (!list || sp || p2sp || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
-		return fail(19, "internal: a model per frame goes with listed whole planar frames of at most %d samples a row, without a chroma mix", vfgs::kTileBlocks * 16);
+	if (mr && (!list || p2sp || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
+		return fail(19, "internal: a model per frame goes with listed whole frames, planar or semi-planar, of at most %d samples a row, without a chroma mix", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) return 0;
 	if (!mr)
@@ -1849,10 +1850,10 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		if (sp)
 		{
 			// (the kernels of semi-planar frames: depth, chroma subsampling y, one-pattern luma, one-pattern chroma; "chroma" in the per-plane figures is the UV plane)
-			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, s.img_one_c));
-			// (grain_sp8_kernel: the same family with the narrowed 8-bit destination)
-			snprintf(li.kernel, sizeof li.kernel, "%s<%d,%d,%s,%s>", dg.out8 ? "grain_sp8_kernel" : "grain_sp_kernel", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false",
-			         s.img_one_c ? "true" : "false");
+			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, img_one_c));
+			// (grain_sp8_kernel: the same family with the narrowed 8-bit destination; grain_spml_kernel: with a model per frame, the form is the models')
+			snprintf(li.kernel, sizeof li.kernel, "%s<%d,%d,%s,%s>", dg.out8 ? "grain_sp8_kernel" : (mr ? "grain_spml_kernel" : "grain_sp_kernel"), 8 + s.bs, s.csuby,
+			         img_one_y ? "true" : "false", img_one_c ? "true" : "false");
 			if (mix)
 			{
 				// (... under the mix: depth, chroma subsampling y; all-one-pattern images)
@@ -3029,7 +3030,8 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
                           unsigned stride, unsigned cstride, hipStream_t stream, DstGeom dg, bool whole = true, unsigned part_y = 0, unsigned part_h = 0,
                           bool seeded = false, const uint32_t* seeds = nullptr,     // seeded: frame f is the frame behind vfgs_set_seed(seeds[f])
                           const int sp_shift = -1,     // >= 0: semi-planar frames, U == V == the UV plane of a frame and cstride its row (run_device)
-                          const vfgs_hip_model* const* models = nullptr)     // a live model of the programmed depth and chroma format per frame (vfgs_hip_add_grain_frame_list_models_dev)
+                          const vfgs_hip_model* const* models = nullptr,     // a live model of the programmed depth and chroma format per frame (vfgs_hip_add_grain_frame_list_models_dev)
+                          const std::function<int()>* late_checks = nullptr)  // what the entry refuses BEHIND the list checks (the semi-planar call with models: 40, then 41)
 {
 	const bool sp = sp_shift >= 0;
 	const bool p2sp = dg.p2sp;        // (planar source, semi-planar destination: dst[f].U == dst[f].V is the UV plane)
@@ -3045,7 +3047,7 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 	for (unsigned f = 0; f < nframes; f++)
 	{
 		if (!src[f].Y || !src[f].U || !src[f].V || !dst[f].Y || !dst[f].U || !dst[f].V) return fail(18, "frame list: frame %u has a null plane", f);
-		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride, !models)) return e;
+		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride, !models && !late_checks)) return e;
 		if ((((uintptr_t)dst[f].Y | (uintptr_t)dst[f].U | (uintptr_t)dst[f].V) & 15)) return fail(7, "plane pointers must be 16-byte aligned");
 	}
 	if (sp && cstride < (width + 15) / 16 * 16)
@@ -3093,6 +3095,8 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			}
 		}
 	}
+	if (late_checks)
+		if (int e = (*late_checks)()) return e;
 	if (models)
 	{
 		// (what run_device would only find behind the first launch of a list of several: refused here, before anything moves)
@@ -3364,6 +3368,49 @@ int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfg
 	}
 	return run_frame_list(ps.data(), src != dst ? pd.data() : ps.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), DstGeom(), true, 0, 0,
 	                      seeds != nullptr, seeds, (int)sample_shift);
+}
+
+// ... with a model per frame (vfgs_hip.h): the list checks of the call above, then its refusals (40), then those of the planar call with models
+// (41); then a frame list that is both (run_frame_list cuts it into runs of one form, run_device takes sp_shift and the ModelRun together).
+int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst, const vfgs_hip_model* const* models,
+                                                const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                                unsigned uv_stride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	if (!src || !dst) return fail(18, "frame list: null list");
+	const std::function<int()> late = [&]() -> int {
+		if (s.csubx != 2)
+			return fail(40, "semi-planar frames with models: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
+		if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
+			return fail(40, "semi-planar frames with models: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
+		if (width > (unsigned)vfgs::kTileBlocks * 16)
+			return fail(40, "semi-planar frames with models: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
+		if (!models) return fail(41, "semi-planar frames with models: null list of models for %u frames", nframes);
+		for (unsigned f = 0; f < nframes; f++)
+		{
+			const vfgs_hip_model* m = models[f];
+			if (!model_live(m)) return fail(41, "semi-planar frames with models: the model of frame %u is %s", f, m ? "not a live model (released?)" : "null");
+			if (m->bs != s.bs || m->csubx != s.csubx || m->csuby != s.csuby)
+				return fail(41, "semi-planar frames with models: the model of frame %u was captured at depth %d, chroma subsampling %d,%d; programmed: depth %d, %d,%d", f,
+				            8 + m->bs, m->csubx, m->csuby, 8 + s.bs, s.csubx, s.csuby);
+		}
+		if (mix_active())
+			return fail(41, "semi-planar frames with models: a chroma mix is active; the mix is one per launch, not one per model (clear it, or grain such pictures with the calls that honour it)");
+		return 0;
+	};
+	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd;
+	for (unsigned f = 0; f < nframes; f++) ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};
+	if (src != dst)
+	{
+		pd.resize(nframes);
+		for (unsigned f = 0; f < nframes; f++) pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
+	}
+	return run_frame_list(ps.data(), src != dst ? pd.data() : ps.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), DstGeom(), true, 0, 0,
+	                      seeds != nullptr, seeds, (int)sample_shift, models, &late);
 }
 
 // ... with the narrowed 8-bit destination (P010 / P210 / P012 in, NV12 / NV16 out): the call above with a destination geometry of its own.

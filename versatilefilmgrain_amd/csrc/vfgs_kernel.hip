@@ -32,7 +32,9 @@
 //     them into one planar Cb unit and one planar Cr unit ("UV walk" below); with the narrowed 8-bit destination (P010 in, NV12 out): grain_sp8_kernel,
 //     the same two walks with OUT8 -- a UV lane stores ONE 16-byte unit of Cb/Cr byte pairs;
 //   * a PLANAR source with a semi-planar destination (software-decoded pictures onto a display surface): grain_p2sp_kernel / grain_p2sp8_kernel, the same
-//     two walks again -- a UV lane loads one 16-byte unit from the Cb row and one from the Cr row instead of splitting 32 bytes of an interleaved row.
+//     two walks again -- a UV lane loads one 16-byte unit from the Cb row and one from the Cr row instead of splitting 32 bytes of an interleaved row;
+//   * a MODEL PER FRAME (captured table images, FrameTable::model[]): grain_ml_kernel for planar frames, grain_spml_kernel for semi-planar ones -- the
+//     walks above with the tables, the clip bounds and the packed form's shift taken from the workgroup's frame instead of the launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -683,7 +685,7 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     SP = 2 (luma planes of grain_p2sp_kernel / grain_p2sp8_kernel: a PLANAR source, a semi-planar destination): the source is read as it lies,
 //     low-aligned -- nothing is shifted down -- the results go up or are narrowed as above, and the destination has a geometry of its own
 //     (dpitch, drowbytes) at either container size.
-//   * MODELS (grain_ml_kernel: a model per frame): the table image, the clip bounds and the packed form's shift are those of the
+//   * MODELS (grain_ml_kernel, and with SP the luma planes of grain_spml_kernel: a model per frame): the table image, the clip bounds and the packed form's shift are those of the
 //     workgroup's FRAME -- FrameTable::model[f] points at a ModelRecord with the image behind it -- fetched with scalar loads (the pointer from
 //     the kernel arguments, the record through it) in front of the image loads; everything they feed stays wave-uniform.  Without the flag
 //     the values are the launch's, from KernelArgs, and nothing of this exists.
@@ -715,7 +717,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
-	static_assert(!MODELS || (!OUT8 && !WIDE && !PERSIST && !MIX && !SP), "a model per frame: the plain planar walk, one task per workgroup");
+	static_assert(!MODELS || (!OUT8 && !WIDE && !PERSIST && !MIX && SP != 2), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup");
 	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
@@ -1359,7 +1361,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // pd.rowbytes describe ONE component's source row, the range check is per component row) -- the two planar units the split would have produced,
 // low-aligned as they lie: no v_perm_b32, no shift down.  Everything behind the load is the walk above; the destination always has a geometry
 // of its own (pd.dpitch; pd.drowbytes = ONE component's bytes of a destination row, the UV row holds twice as many).
-template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false>
+//
+// MODELS (UV workgroups of grain_spml_kernel: a model per frame): both components' tables, the chroma clip bounds and the packed
+// form's shift are those of the workgroup's FRAME, as in run_plane_rw MODELS -- FrameTable::model[f] from the kernel arguments, the ModelRecord
+// through it with scalar loads, in front of the table loads; everything they feed stays wave-uniform.  Without the flag nothing of this exists.
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, bool MODELS = false>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
@@ -1378,6 +1384,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of them belong to the lane before its own
 	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0 && !MIX), "the narrowed destination exists for 16-bit containers, without the mix");
 	static_assert(!PLANAR || !MIX, "a planar source has no mix form");
+	static_assert(!MODELS || (!MIX && !OUT8 && !PLANAR), "a model per frame: the plain UV walk");
 	constexpr bool DGEO = OUT8 || PLANAR;                // the destination has a geometry of its own
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
@@ -1412,10 +1419,23 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int STEP = kWavesPerWG * 64 * 16;
 	constexpr int NIT = (IMG + STEP - 1) / STEP;
 	u32x4 tmp[NIT];
+	// MODELS: my frame's model -- its record (constant address space: scalar loads) and the image behind it
+	const uint8_t* mtables = nullptr;
+	uint32_t mlo2 = 0, mhi2 = 0;
+	int mpk_shift = 0;
+	if constexpr (MODELS)
+	{
+		typedef const uint32_t __attribute__((address_space(4)))* crec_t;
+		const uint8_t* const mp = ft.model[f];
+		const crec_t rec = (crec_t)(uintptr_t)mp;
+		mlo2 = rec[1]; mhi2 = rec[3];
+		mpk_shift = (int)rec[4];
+		mtables = mp + kModelRecordBytes;
+	}
 	{
 		// (the device image holds [LUT Cb][bank][LUT Cr][bank]: one-pattern form -- both sub-images as they are; general form -- LDS offset o
 		// comes from Cb's LUT, Cr's LUT, Cb's copy of the bank)
-		const __amdgpu_buffer_rsrc_t irs = make_rsrc(a.tables + img_off, 2 * CIMG);
+		const __amdgpu_buffer_rsrc_t irs = make_rsrc((MODELS ? mtables : a.tables) + img_off, 2 * CIMG);
 #pragma unroll
 		for (int it = 0; it < NIT; it++)
 		{
@@ -1518,7 +1538,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 		return;
 
 	// ---- per lane constants ------------------------------------------------------------------------------------------
-	const uint32_t lo2 = a.lo2[1], hi2 = a.hi2[1];
+	const uint32_t lo2 = MODELS ? mlo2 : a.lo2[1], hi2 = MODELS ? mhi2 : a.hi2[1];
 	const uint32_t idx0 = (uint32_t)lane * M::BPL * 4;
 	const int cl = lane * M::BPL - 1;
 	auto lane_up = [](uint32_t old, uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xf, 0xf, false); };    // wave_shr:1
@@ -1705,9 +1725,9 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 #pragma unroll
 						for (int rr = 0; rr < NR; rr++) up.pa[rr] = OV ? *(const uint32_t*)(pe + PT + (2 * c + 1) * kParamTableBytes + (u * BPS + rr) * 4) : 0u;
 						if constexpr (MIX)
-							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG, true>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, ti);
+							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG, true>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, MODELS ? mpk_shift : a.pk_shift, ti);
 						else
-							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, a.pk_shift, t);
+							grain_unit<DEPTH, BW, OV, ONE, ONE, NEG>(cl_, t, rp, up, lutb, rowoff, uprowoff, OV ? wc_ : 0, OV ? wu_ : 0, edge_on, false, lo2, hi2, MODELS ? mpk_shift : a.pk_shift, t);
 					}
 					if constexpr (OUT8)
 					{
@@ -1779,6 +1799,26 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp_kernel(
 		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
 		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
+}
+
+// Semi-planar frames with A MODEL PER FRAME (KernelArgs::sp_kernel AND models_kernel; vfgs_hip_add_grain_sp_frame_list_models_dev):
+// grain_sp_kernel's grid, numbering, launch bounds and LDS allocation; listed frames whose models share the form (ONEY, ONEC) of their images
+// and nothing else.  A workgroup, luma or UV, stages ITS frame's tables and clips with ITS frame's bounds (run_plane_rw / run_uv_sp MODELS).
+template <int DEPTH, int CSUBY, bool ONEY, bool ONEC>
+__global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_spml_kernel(const KernelArgs a, const FrameTable ft)
+{
+	constexpr ImageLayout L = image_layout(2, CSUBY, ONEY, ONEC, DEPTH == 8);
+	__shared__ __attribute__((aligned(16))) uint8_t lds[sp_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, ONEC))];
+
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
+	const int r = (int)(blockIdx.x >> a.lfronts);
+	if (f >= a.nframes) return;
+	if (r < a.pd[0].wgs)
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, false, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // The kernels of semi-planar frames with a narrowed destination (KernelArgs::sp_kernel AND out8: P010 / P210 / P012 in, NV12 / NV16 out;
@@ -1967,6 +2007,17 @@ static hipError_t launch_sp(const KernelArgs& a, const FrameTable& ft, bool oney
 }
 
 template <int DEPTH, int CSUBY>
+static hipError_t launch_spml(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
+{
+	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
+	if (oney && onec) hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
+	else if (oney) hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
+	else if (onec) hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
+	else hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
+	return hipGetLastError();
+}
+
+template <int DEPTH, int CSUBY>
 static hipError_t launch_sp8(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
 {
 	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
@@ -2023,10 +2074,20 @@ static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int cs
 {
 	if (a.models_kernel)
 	{
-		// a model per frame: listed whole planar frames, rows of one parameter table, no mix, every frame with a model image (the host refuses everything else)
-		if (a.models_kernel != 1 || a.sp_kernel || a.mix_kernel || out8 || wide || persist || !a.listed) return hipErrorInvalidValue;
+		// a model per frame: listed whole frames, planar or semi-planar (not a planar source with a semi-planar destination), rows of one parameter
+		// table, no mix, every frame with a model image (the host refuses everything else)
+		if (a.models_kernel != 1 || (a.sp_kernel != 0 && a.sp_kernel != 1) || a.mix_kernel || out8 || wide || persist || !a.listed) return hipErrorInvalidValue;
 		for (int f = 0; f < a.nframes; f++)
 			if (!ft.model[f] || ((uintptr_t)ft.model[f] & 15)) return hipErrorInvalidValue;
+		if (a.sp_kernel)
+		{
+			// (semi-planar frames: the conditions of the branch below)
+			if (csubx != 2 || a.y0 != 0) return hipErrorInvalidValue;
+			if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
+			if (csuby == 2) return launch_spml<D, 2>(a, ft, oney, onec, grid, stream);
+			if (csuby == 1) return launch_spml<D, 1>(a, ft, oney, onec, grid, stream);
+			return hipErrorInvalidValue;
+		}
 		if (csubx == 2 && csuby == 2) return launch_ml<D, 2, 2>(a, ft, oney, onec, grid, stream);
 		if (csubx == 2 && csuby == 1) return launch_ml<D, 2, 1>(a, ft, oney, onec, grid, stream);
 		if (csubx == 1 && csuby == 1) return launch_ml<D, 1, 1>(a, ft, oney, onec, grid, stream);

@@ -283,7 +283,7 @@ struct KernelArgs {
 	PlaneDesc pd[2];
 	const uint32_t* stream;   // LFSR bit stream cache (device), bit m = word[m>>5] >> (m&31)
 	uint32_t stream_bytes;
-	// 1: grain_ml_kernel serves the launch (listed frames; FrameTable::model[f] is frame f's model image and `tables` below frame 0's table
+	// 1: grain_ml_kernel -- with sp_kernel == 1: grain_spml_kernel -- serves the launch (listed frames; FrameTable::model[f] is frame f's model image and `tables` below frame 0's table
 	// image).  The field sits HERE, in the four bytes that used to be padding in front of the pointer below: the frame table is the kernel
 	// argument BEHIND this structure, so a field appended at the end would move every plane pointer the kernels of before load (the
 	// static_assert below the structure holds its size).

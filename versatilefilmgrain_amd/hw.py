@@ -126,6 +126,7 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_model_release.restype = None
     lib.vfgs_hip_model_info.argtypes = [vp, C.POINTER(i)]
     lib.vfgs_hip_add_grain_frame_list_models_dev.argtypes = [fp, fp, C.POINTER(vp), sp, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_sp_frame_list_models_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -196,6 +197,7 @@ EXPORTS = [
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
     "vfgs_hip_model_capture", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
+    "vfgs_hip_add_grain_sp_frame_list_models_dev",
 ]
 
 
@@ -403,6 +405,19 @@ class VfgsHip:
         assert len(s) == len(d) == len(models) and (seeds is None or len(seeds) == len(s))
         arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
         self._ck(self.lib.vfgs_hip_add_grain_frame_list_models_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, cstride, stream))
+
+    def add_grain_sp_frame_list_models_dev(self, src, dst, models, seeds, width, height, stride, uv_stride, sample_shift, stream=0):
+        """Semi-planar frames with a model per picture: src / dst / seeds / geometry / sample_shift as in add_grain_sp_frame_list_dev (dst is
+        src, or None: in place), models as in add_grain_frame_list_models_dev.  Frame f is grained as if models[f]'s state were programmed
+        (and, with seeds, vfgs_set_seed(seeds[f]) called) in front of a one-frame add_grain_sp_frame_list_dev without a mix; one launch per
+        run of at most 32 frames whose models share the form of their images.  The programmed state is unchanged.  VfgsHipError 40: csubx
+        != 2, a bad sample_shift, width > 8192; 41: a null / released model, a model of another depth or chroma format, an active chroma mix."""
+        s = self.sp_frame_list(src)
+        d = s if (dst is None or dst is src) else self.sp_frame_list(dst)
+        assert len(s) == len(d) == len(models) and (seeds is None or len(seeds) == len(s))
+        arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
+        self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_models_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
+                                                                      sample_shift, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
