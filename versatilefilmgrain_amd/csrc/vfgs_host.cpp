@@ -17,7 +17,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -1487,31 +1486,87 @@ void release_models()
 	g_models_left.clear();
 }
 
-// Core: launch the kernel over `nframes` frames, lines [part_y, part_y+part_h) of each.
-struct DstGeom {          // destination geometry when it differs from the source's (8-bit output of a 10- or 12-bit path)
-	bool out8 = false;
-	unsigned stride = 0, cstride = 0;
-	uint64_t ypitch = 0, cpitch = 0;
-	// a planar source with a semi-planar destination (vfgs_hip_add_grain_frame_list_to_sp_dev / _to_sp8_dev): dU == dV is the UV plane, stride / cstride
-	// above are the destination's rows in ITS containers (out8: bytes) and the samples go `p2sp_shift` bits up in them
-	bool p2sp = false;
-	unsigned p2sp_shift = 0;
+// ------------------------------------------------------------------------------------
+// one grain call: what an entry asks of run_device
+
+enum class Surface {
+	planar,            // three planes in, three planes out
+	semiplanar,        // sU == sV and dU == dV: the UV plane of interleaved Cb/Cr pairs, cstride its row in containers (KernelArgs::sp_kernel 1)
+	to_semiplanar,     // a planar source, dU == dV the UV plane (vfgs_hip_add_grain_frame_list_to_sp_dev / _to_sp8_dev; KernelArgs::sp_kernel 2)
 };
 
-int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV, unsigned width,
-               unsigned frame_y, unsigned frame_h, unsigned part_y, unsigned part_h, unsigned stride, unsigned cstride,
-               unsigned nframes, uint64_t ypitch, uint64_t cpitch, hipStream_t stream, DstGeom dg = DstGeom(),
-               const vfgs::FrameTable* list = nullptr,     // list: the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
-               const uint32_t* seeds = nullptr,            // seeds: frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
-               const int sp_shift = -1,                    // >= 0: semi-planar frames (sU == sV, dU == dV: the UV plane, cstride its row in containers), samples that many bits up
-               const ModelRun* mr = nullptr)               // a model per frame (run_frame_list with models; with sp_shift >= 0: on semi-planar frames): list->model[] holds their images, the programmed state's image stays out of it
+struct DstGeom {          // destination geometry when it differs from the source's: the 8-bit output of a 10- or 12-bit path, the surface of Surface::to_semiplanar
+	bool out8 = false;
+	unsigned stride = 0, cstride = 0;     // (to_semiplanar: the destination's rows in ITS containers -- out8: bytes)
+	uint64_t ypitch = 0, cpitch = 0;
+};
+
+// Lines [part_y, part_y + part_h) of `nframes` frames whose lines [frame_y, frame_y + frame_h) the seed registers advance over.
+struct GrainCall {
+	const void *sY = nullptr, *sU = nullptr, *sV = nullptr;     // the planes of frame 0
+	void *dY = nullptr, *dU = nullptr, *dV = nullptr;
+	unsigned width = 0, stride = 0, cstride = 0;          // (strides: samples)
+	unsigned frame_y = 0, frame_h = 0, part_y = 0, part_h = 0;
+	unsigned nframes = 1;
+	uint64_t ypitch = 0, cpitch = 0;                      // frames at a constant pitch (bytes; unused with a list)
+	hipStream_t stream = nullptr;
+	Surface surface = Surface::planar;
+	unsigned sample_shift = 0;                            // semi-planar containers: the samples sit that many bits up in them
+	DstGeom dg;
+	const vfgs::FrameTable* list = nullptr;               // the planes of the frames (sY.. / dY.. = those of frame 0, the pitches unused)
+	const uint32_t* seeds = nullptr;                      // frame f is the frame behind vfgs_set_seed(seeds[f]) (whole frames from line 0, listed)
+	const ModelRun* mr = nullptr;                         // a model per frame (launch_list): list->model[] holds their images, the programmed state's image stays out of it
+
+	// (an entry writes its call as one chain of these)
+	GrainCall& in_place(void* Y, void* U, void* V) { return copy(Y, U, V, Y, U, V); }
+	GrainCall& copy(const void* Y, const void* U, const void* V, void* toY, void* toU, void* toV)
+	{
+		sY = Y; sU = U; sV = V; dY = toY; dU = toU; dV = toV;
+		return *this;
+	}
+	GrainCall& rows(unsigned w, unsigned str, unsigned cstr) { width = w; stride = str; cstride = cstr; return *this; }
+	GrainCall& whole(unsigned height) { return part(height, 0, height); }
+	GrainCall& part(unsigned frame_height, unsigned y, unsigned h, unsigned from = 0) { frame_y = from; frame_h = frame_height; part_y = y; part_h = h; return *this; }
+	GrainCall& frames(unsigned n, uint64_t yp, uint64_t cp) { nframes = n; ypitch = yp; cpitch = cp; return *this; }
+	GrainCall& on(hipStream_t st) { stream = st; return *this; }
+	GrainCall& to(Surface sf, unsigned shift) { surface = sf; sample_shift = shift; return *this; }
+	GrainCall& dst_rows(bool out8, unsigned str, unsigned cstr, uint64_t yp = 0, uint64_t cp = 0) { dg = DstGeom{out8, str, cstr, yp, cp}; return *this; }
+};
+
+// One run_device: the call, and what its phases hand to each other.
+struct Launch : GrainCall {
+	State& s;
+	const bool sp, p2sp;                    // (p2sp: planar source, semi-planar destination -- `sp`, both semi-planar, is false then)
+	KernelArgs a{};
+	bool nothing = false;                   // admitted, and nothing to launch (no lines, no frames)
+	unsigned nblk = 0, sz = 1, nparts = 1;  // nparts: passes over the parameter table a row needs
+	bool wide = false, mix = false;
+	int nbr_stripe = 0;
+	uint64_t yext = 0, cext = 0;            // bytes of a luma / chroma plane's stripe
+	bool form_one_y = false, form_one_c = false;     // the form the table image will have (bind_tables)
+	bool img_one_y = false, img_one_c = false;       // the form of the image(s) this launch reads
+	uint64_t first_cur = 0, first_up = 0, second_cur = 0, lo = ~0ull, hi = 0;     // stream positions (plan_seeds)
+	bool stripes = false, persist = false;  // the stream comes as a StripeStream image; persistent luma workgroups
+	long per_frame = 0, grid = 0;
+
+	Launch(State& state, const GrainCall& c) : GrainCall(c), s(state), sp(surface == Surface::semiplanar), p2sp(surface == Surface::to_semiplanar) {}
+	int admit();
+	void plan_planes();
+	int plan_seeds();
+	void seeded_done();
+	int bind_tables();
+	int bind_stream();
+	int plan_grid();
+	int launch();
+	void record_launch();
+};
+
+// Everything that refuses the call; changes no state except what digest_pluts digests.
+int Launch::admit()
 {
-	State& s = S();
 	if (list && nframes > (unsigned)vfgs::kListFrames) return fail(19, "internal: a listed launch holds at most %d frames", vfgs::kListFrames);
 	if (int e = ensure_init(-1)) return e;
 	if (int e = check_geometry(s, sY, sU, sV, width, stride, cstride, !mr)) return e;
-	const bool sp = sp_shift >= 0;
-	const bool p2sp = dg.p2sp;            // planar source, semi-planar destination: `sp` (both semi-planar) is false
 	if (p2sp && !dg.out8)
 	{
 		// (the destination's rows in containers of the source's size: Y, and a UV row as long as it)
@@ -1536,19 +1591,19 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	if (seeds && (frame_y != 0 || !list)) return fail(19, "internal: seeds belong to lists of frames that begin at line 0");
 	if (sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
-	if (p2sp && (sp || !list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
+	if (p2sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (mr && (!list || p2sp || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
 		return fail(19, "internal: a model per frame goes with listed whole frames, planar or semi-planar, of at most %d samples a row, without a chroma mix", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
-	if (part_h == 0 || nframes == 0) return 0;
+	if (part_h == 0 || nframes == 0) { nothing = true; return 0; }
 	if (!mr)
 		if (int e = check_luts(s)) return e;     // before any state moves: a refused call leaves the seed registers alone
 
-	const unsigned nblk = (width + 15) / 16;
-	const unsigned sz = s.bs ? 2 : 1;
+	nblk = (width + 15) / 16;
+	sz = s.bs ? 2 : 1;
 	const uint64_t crows = (uint64_t)(part_y + part_h - 1) / s.csuby - part_y / s.csuby + 1;
-	const uint64_t yext = (uint64_t)part_h * stride * sz, cext = crows * cstride * sz;
+	yext = (uint64_t)part_h * stride * sz; cext = crows * cstride * sz;
 	if (yext >= 0x80000000ull || cext >= 0x80000000ull)
 		return fail(15, "a plane stripe of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)yext);
 	if (p2sp)
@@ -1557,32 +1612,26 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		if (dyext >= 0x80000000ull || dcext >= 0x80000000ull)
 			return fail(15, "a destination plane of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)std::max(dyext, dcext));
 	}
-	KernelArgs a{};
 	a.src[0] = (const uint8_t*)sY; a.src[1] = (const uint8_t*)sU; a.src[2] = (const uint8_t*)sV;
 	a.dst[0] = (uint8_t*)dY; a.dst[1] = (uint8_t*)dU; a.dst[2] = (uint8_t*)dV;
 	a.y0 = (int)part_y;
 	a.nblk = (int)nblk;
-	const int nbr_stripe = (int)(((part_y + part_h - 1) >> 4) - (part_y >> 4) + 1);
+	nbr_stripe = (int)(((part_y + part_h - 1) >> 4) - (part_y >> 4) + 1);
 	a.nbrows = nbr_stripe;
 	a.nframes = (int)nframes;
 	a.listed = list ? 1 : 0;
 	a.lo2[0] = (uint32_t)(s.ymin << s.bs) * 0x10001u; a.hi2[0] = (uint32_t)(s.ymax << s.bs) * 0x10001u;
 	a.lo2[1] = (uint32_t)(s.cmin << s.bs) * 0x10001u; a.hi2[1] = (uint32_t)(s.cmax << s.bs) * 0x10001u;
 	a.pk_shift = s.scale_shift;     // (read by the 8-bit one-pattern forms only: vfgs_layout.h "packed 16-bit form"; 8..13, check_state)
-	// Geometry: a wave streams whole rows (positions = the row's units + the one behind them: the lanes compute bytes shifted
-	// by part of a unit); a workgroup = kWavesPerWG x rw_rpw rows of one block row, VFGS_RW_WG_BYTES where the block row allows.
-	// Launches that leave wave slots empty get workgroups of half the rows (single frames up to 2160p).
-	const unsigned nparts = (nblk + vfgs::kTileBlocks - 1) / vfgs::kTileBlocks;     // passes over the parameter table a row needs
-	int rw_shrink = 0;                      // halvings of the rows per wave (small launches)
-	bool form_one_y = false, form_one_c = false;   // the form the table image will have (upload_tables below)
+	nparts = (nblk + vfgs::kTileBlocks - 1) / vfgs::kTileBlocks;     // passes over the parameter table a row needs
 	digest_pluts(s);
-	const bool wide = nparts > 1;           // rows walked in parts: not every form of the table image has such a kernel (image_form)
+	wide = nparts > 1;           // rows walked in parts: not every form of the table image has such a kernel (image_form)
 	if (mr) { form_one_y = mr->one_y; form_one_c = mr->one_c; }     // (the form the run's models were captured in)
 	else if (image_is_current(s, wide)) { form_one_y = s.img_one_y; form_one_c = s.img_one_c; }
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
 	// (the semi-planar call refuses the same cases under its own code, 40: the two entries stay congruent on the planar picture)
-	const bool mix = mix_active();
+	mix = mix_active();
 	if (mix && p2sp) return fail(19, "internal: a planar source with a semi-planar destination under a chroma mix");     // (refused with code 40 at the entry)
 	const int mix_code = sp ? 40 : 38;
 	const char* const mix_who = sp ? "semi-planar frames: " : "";
@@ -1594,6 +1643,15 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	if (mix && &s != &g_states[0])
 		return sp ? fail(19, "internal: semi-planar frames on a device of vfgs_hip_init_devices")
 		          : fail(38, "a chroma mix is active: not supported on the devices of vfgs_hip_init_devices");
+	return 0;
+}
+
+// Geometry: a wave streams whole rows (positions = the row's units + the one behind them: the lanes compute bytes shifted
+// by part of a unit); a workgroup = kWavesPerWG x rw_rpw rows of one block row, VFGS_RW_WG_BYTES where the block row allows.
+// Launches that leave wave slots empty get workgroups of half the rows (single frames up to 2160p).
+void Launch::plan_planes()
+{
+	int rw_shrink = 0;                      // halvings of the rows per wave (small launches)
 	for (int pass = 0; pass < 3; pass++)
 	{
 		long waves = 0;
@@ -1633,26 +1691,24 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		if (pass < 2 && waves * 100 < VFGS_RW_MIN_FILL_PCT * slots && (a.pd[0].rw_rpw > 1 || a.pd[1].rw_rpw > 1)) { rw_shrink++; continue; }
 		break;
 	}
+}
 
-	// seeds: frames 0 and 1 run the state machine (vfgs_hw.c:291-298, 309-310; one step per block row); from the end of frame 0 on
-	// all four registers move by the same amount per frame -- a frame of nbr block rows rotates nbr - 1 times (not at line 0) and
-	// every rotation moves line_rnd, and line_rnd_up behind it, by one row of blocks: G = f (nbr - 1) + r, SURVEY 8a -- so the
-	// frames behind them are one addition each register, whatever the batch size
-	//
-	// With a seed per frame every frame begins at bit 0 of a stream of its own: block row b reads its registers at b x nblk and, for the row
-	// above it, (b - 1) x nblk (the machine run from zeroed registers), the same positions in every frame.  The registers themselves move
-	// behind the launch (seeded_done): a call that fails before it is queued leaves them where they were.
-	uint64_t first_cur = 0, first_up = 0, second_cur = 0, lo = ~0ull, hi = 0;
+// seeds: frames 0 and 1 run the state machine (vfgs_hw.c:291-298, 309-310; one step per block row); from the end of frame 0 on
+// all four registers move by the same amount per frame -- a frame of nbr block rows rotates nbr - 1 times (not at line 0) and
+// every rotation moves line_rnd, and line_rnd_up behind it, by one row of blocks: G = f (nbr - 1) + r, SURVEY 8a -- so the
+// frames behind them are one addition each register, whatever the batch size
+//
+// With a seed per frame every frame begins at bit 0 of a stream of its own: block row b reads its registers at b x nblk and, for the row
+// above it, (b - 1) x nblk (the machine run from zeroed registers), the same positions in every frame.  The registers themselves move
+// behind the launch (seeded_done): a call that fails before it is queued leaves them where they were.
+int Launch::plan_seeds()
+{
 	if (seeds)
 	{
 		const uint64_t b = part_y >> 4;
 		first_cur = b * nblk;
 		first_up = b ? (b - 1) * nblk : 0;
 	}
-	auto seeded_done = [&] {     // the state vfgs_set_seed(seeds[nframes - 1]) + one whole frame leaves
-		load_seed(s, seeds[nframes - 1]);
-		advance_seeds(s, 0, frame_h, nblk, 0);
-	};
 	for (unsigned f = 0; f < nframes && f < 2 && !seeds; f++)
 	{
 		StripePlan p = advance_seeds(s, frame_y, frame_h, nblk, part_y);
@@ -1669,11 +1725,22 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		s.rnd += more; s.rnd_up += more; s.line_rnd += more; s.line_rnd_up += more;
 		hi = std::max(hi, second_cur + more + (uint64_t)nbr_stripe * nblk);
 	}
-	// Images are uploaded on the stream of the call that needs them first; a call on ANOTHER stream waits (once) for that
-	// upload, and a slot is only overwritten after all its readers (SlotGuard)
+	return 0;
+}
+
+void Launch::seeded_done()     // the state vfgs_set_seed(seeds[nframes - 1]) + one whole frame leaves
+{
+	load_seed(s, seeds[nframes - 1]);
+	advance_seeds(s, 0, frame_h, nblk, 0);
+}
+
+// Images are uploaded on the stream of the call that needs them first; a call on ANOTHER stream waits (once) for that
+// upload, and a slot is only overwritten after all its readers (SlotGuard)
+int Launch::bind_tables()
+{
 	if (mr)
 	{
-		// (the images are the models' own, made visible to `stream` by run_frame_list_models; the programmed state's image is neither built nor looked at)
+		// (the images are the models' own, made visible to `stream` by launch_list; the programmed state's image is neither built nor looked at)
 		a.models_kernel = 1;
 		a.tables = list->model[0] + vfgs::kModelRecordBytes;
 		a.lo2[0] = mr->first.lo2[0]; a.lo2[1] = mr->first.lo2[1]; a.hi2[0] = mr->first.hi2[0]; a.hi2[1] = mr->first.hi2[1];
@@ -1686,7 +1753,13 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		a.tables = (const uint8_t*)s.tables_ring.current();
 	}
 	// the form of the image(s) this launch reads
-	const bool img_one_y = mr ? mr->one_y : s.img_one_y, img_one_c = mr ? mr->one_c : s.img_one_c;
+	img_one_y = mr ? mr->one_y : s.img_one_y; img_one_c = mr ? mr->one_c : s.img_one_c;
+	return 0;
+}
+
+// The LFSR stream the launch reads: an image of per-frame streams (seeds), the runs of a batch of stripes alone, or the contiguous window.
+int Launch::bind_stream()
+{
 	// A batch of stripes that are a small part of their frames (a rank of a stripe split) reads short runs of the
 	// stream that lie a whole frame apart: those runs alone, each the jump of the one before (StripeStream).  One segment =
 	// [a word in front of the row above the stripe's first, 64 bits behind its last block].
@@ -1694,8 +1767,8 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	const uint64_t seg_bits = 32 + (uint64_t)nblk + (uint64_t)nbr_stripe * nblk + 64;
 	const unsigned seg_words = (unsigned)((seg_bits + 31) / 32) + 1;
 	static const bool jump_on = [] { const char* e = getenv("VFGS_HIP_STRIPE_JUMP"); return !(e && e[0] == '0'); }();
-	const bool stripes = !seeds && jump_on && nframes >= 2 && first_cur >= (uint64_t)nblk + 32 && first_up + nblk + 32 >= first_cur &&
-	                     (uint64_t)seg_words * 32 * 4 <= frame_step * 3;      // (the segments are at most three quarters of what lies between them)
+	stripes = !seeds && jump_on && nframes >= 2 && first_cur >= (uint64_t)nblk + 32 && first_up + nblk + 32 >= first_cur &&
+	          (uint64_t)seg_words * 32 * 4 <= frame_step * 3;      // (the segments are at most three quarters of what lies between them)
 	s.stripe_stream_last = stripes;
 	s.seeded_stream_last = seeds != nullptr;
 	if (seeds)
@@ -1731,16 +1804,20 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		a.up_bit0 = (uint32_t)(first_up - s.lfsr.base_bit());
 		a.frame_bit_step = (uint32_t)frame_step;
 	}
+	return 0;
+}
 
+// per_frame == 0: nothing to launch
+int Launch::plan_grid()
+{
 	// one workgroup per (frame, plane, block row, part of it), numbered in memory order
-	const long per_frame = (long)a.pd[0].wgs + ((sp || p2sp) ? 1L : 2L) * a.pd[1].wgs;     // (semi-planar frames: one UV workgroup serves Cb and Cr)
+	per_frame = (long)a.pd[0].wgs + ((sp || p2sp) ? 1L : 2L) * a.pd[1].wgs;     // (semi-planar frames: one UV workgroup serves Cb and Cr)
 	if (per_frame > 0x3fffffffL || nframes > 65535) return fail(14, "launch too large");
-	if (per_frame == 0) { if (seeds) seeded_done(); return 0; }
+	if (per_frame == 0) return 0;
 	// General-form luma of small pictures: a workgroup stages 36 KB of tables for 15-30 KB of samples.  Where a launch holds several
 	// rounds of luma workgroups, P persistent ones share the luma tasks instead (task t -> workgroup t % P, so they sweep the frames
 	// in memory order together); chroma keeps one workgroup per task behind them in the grid.
-	bool persist = false;
-	long grid = per_frame;
+	grid = per_frame;
 	// (10 and 12 bit -- the same bytes through the same LDS image -- only: at 8 bit the general-form kernels are bound by their LDS instructions, and confining luma to P < all workgroup
 	// slots costs them 7 %; at 10 bit 1080p gains 6 % at 32 and 64 frames per launch, 2160p nothing: profiles/r04_ab2_persistent_luma.log)
 	if (VFGS_PERSIST_MIN_TASKS > 0 && !sp && !p2sp && !mr && s.bs != 0 && !wide && !img_one_y && a.pd[0].wgs > 0 &&
@@ -1767,15 +1844,21 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 	const bool in_region = g_states[0].ov.active && (stream == g_states[0].ov.s[0] || stream == g_states[0].ov.s[1]);
 	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + (sp ? 1 : 2) * cext) >= (64u << 20)) ? 1 : 0;
 #endif
+	return 0;
+}
+
+// The launch -- under a chroma mix over shared luma bytes, two of them.
+int Launch::launch()
+{
 	if (sp)
 	{
 		a.sp_kernel = 1;
-		a.sp_shift2 = (uint32_t)sp_shift * 0x10001u;
+		a.sp_shift2 = sample_shift * 0x10001u;
 	}
 	if (p2sp)
 	{
 		a.sp_kernel = 2;
-		a.sp_shift2 = dg.p2sp_shift * 0x10001u;
+		a.sp_shift2 = sample_shift * 0x10001u;
 	}
 	if (mix)
 	{
@@ -1809,10 +1892,12 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		}
 	}
 	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist, (int)grid, stream));
-	if (seeds) seeded_done();
-	// the stream of the batches behind this one, while the GPU works on this one.  (Failing to work ahead is not a failure of THIS call, which is
-	// queued and whose registers have moved: the next call then builds its image in its own stream.)
-	if (stripes && s.stripes.prepare_next(s.lfsr) != hipSuccess) (void)hipGetLastError();
+	return 0;
+}
+
+// vfgs_hip_last_launch_info(): what the primary state's launch dispatched
+void Launch::record_launch()
+{
 	if (&s == &g_states[0])
 	{
 		vfgs_hip_launch_info& li = g_last_launch;
@@ -1870,6 +1955,28 @@ int run_device(const void* sY, const void* sU, const void* sV, void* dY, void* d
 		}
 		g_last_launch_valid = true;
 	}
+}
+
+// Core: launch the kernel over `nframes` frames, lines [part_y, part_y+part_h) of each.  The order of the phases is the order of the refusals and
+// of the state changes: the pattern LUTs' digest (admit), the seed registers (plan_seeds), the table image (bind_tables), the stream's device copy
+// (bind_stream), the launch, the registers of a seeded call behind it, the next batch's stream, the launch record.
+int run_device(const GrainCall& c)
+{
+	Launch L(S(), c);
+	if (int e = L.admit()) return e;
+	if (L.nothing) return 0;
+	L.plan_planes();
+	if (int e = L.plan_seeds()) return e;
+	if (int e = L.bind_tables()) return e;
+	if (int e = L.bind_stream()) return e;
+	if (int e = L.plan_grid()) return e;
+	if (L.per_frame == 0) { if (c.seeds) L.seeded_done(); return 0; }
+	if (int e = L.launch()) return e;
+	if (c.seeds) L.seeded_done();
+	// the stream of the batches behind this one, while the GPU works on this one.  (Failing to work ahead is not a failure of THIS call, which is
+	// queued and whose registers have moved: the next call then builds its image in its own stream.)
+	if (L.stripes && L.s.stripes.prepare_next(L.s.lfsr) != hipSuccess) (void)hipGetLastError();
+	L.record_launch();
 	return 0;
 }
 
@@ -1937,8 +2044,7 @@ int run_host(void* Y, void* U, void* V, unsigned y, unsigned width, unsigned hei
 	}
 	{
 		InternalLaunch mark;
-		if (int e = run_device(s.stage[0], s.stage[1], s.stage[2], s.stage[0], s.stage[1], s.stage[2], width, y, height, py, ph,
-		                       dpitch[0] / sz, dpitch[1] / sz, 1, 0, 0, s.own_stream))
+		if (int e = run_device(GrainCall().in_place(s.stage[0], s.stage[1], s.stage[2]).rows(width, dpitch[0] / sz, dpitch[1] / sz).part(height, py, ph, y).on(s.own_stream)))
 			return e;
 	}
 	for (int i = 0; i < 3; i++)
@@ -2037,8 +2143,7 @@ int run_host_frames(void* const* Y, void* const* U, void* const* V, unsigned nfr
 		if (!hip(hipEventRecord(P.up_done[k], P.up), "hipEventRecord") || !hip(hipStreamWaitEvent(P.run, P.up_done[k], 0), "hipStreamWaitEvent")) break;
 		{
 			InternalLaunch mark;
-			rc = run_device(P.dev[k][0], P.dev[k][1], P.dev[k][2], P.dev[k][0], P.dev[k][1], P.dev[k][2], width, 0, height, py, ph,
-			                dpitch[0] / sz, dpitch[1] / sz, 1, 0, 0, P.run);
+			rc = run_device(GrainCall().in_place(P.dev[k][0], P.dev[k][1], P.dev[k][2]).rows(width, dpitch[0] / sz, dpitch[1] / sz).part(height, py, ph).on(P.run));
 		}
 		if (rc) break;
 		if (!hip(hipEventRecord(P.run_done[k], P.run), "hipEventRecord") || !hip(hipStreamWaitEvent(P.down, P.run_done[k], 0), "hipStreamWaitEvent")) break;
@@ -2182,8 +2287,7 @@ int lookahead_issue_impl(State& s, int k, unsigned y0, unsigned n)
 	int e;
 	{
 		InternalLaunch mark;
-		e = run_device(sl.dev[0], sl.dev[1], sl.dev[2], sl.dev[0], sl.dev[1], sl.dev[2], la.width, y0, n, y0, n,
-		               la.dpitch[0] / sz, la.dpitch[1] / sz, 1, 0, 0, la.run);
+		e = run_device(GrainCall().in_place(sl.dev[0], sl.dev[1], sl.dev[2]).rows(la.width, la.dpitch[0] / sz, la.dpitch[1] / sz).part(n, y0, n, y0).on(la.run));
 	}
 	la.spec[0] = s.rnd; la.spec[1] = s.rnd_up; la.spec[2] = s.line_rnd; la.spec[3] = s.line_rnd_up;
 	s.rnd = keep[0]; s.rnd_up = keep[1]; s.line_rnd = keep[2]; s.line_rnd_up = keep[3];
@@ -2973,81 +3077,97 @@ void vfgs_hip_shutdown(void)
 	g_ndev = 1;
 }
 
-int vfgs_hip_add_grain_stripe_dev(void* dY, void* dU, void* dV, unsigned y, unsigned width, unsigned height,
-                                  unsigned stride, unsigned cstride, void* stream)
-{
-	std::lock_guard<std::mutex> g(g_mu);
-	S().gen++;
-	return run_device(dY, dU, dV, dY, dU, dV, width, y, height, y, height, stride, cstride, 1, 0, 0, pick_stream(stream));
-}
+// ---- what several entries check, written once ----
 
-int vfgs_hip_add_grain_frame_dev(void* dY, void* dU, void* dV, unsigned width, unsigned height,
-                                 unsigned stride, unsigned cstride, void* stream)
+static int check_part(unsigned part_y, unsigned part_h, unsigned frame_h)
 {
-	std::lock_guard<std::mutex> g(g_mu);
-	S().gen++;
-	return run_device(dY, dU, dV, dY, dU, dV, width, 0, height, 0, height, stride, cstride, 1, 0, 0, pick_stream(stream));
-}
-
-int vfgs_hip_add_grain_frame_part_dev(void* dY, void* dU, void* dV, unsigned width, unsigned frame_height,
-                                      unsigned part_y, unsigned part_height, unsigned stride, unsigned cstride, void* stream)
-{
-	std::lock_guard<std::mutex> g(g_mu);
-	S().gen++;
 	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
-	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
-	return run_device(dY, dU, dV, dY, dU, dV, width, 0, frame_height, part_y, part_height, stride, cstride, 1, 0, 0, pick_stream(stream));
+	if (part_y > frame_h || part_h > frame_h - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
+	return 0;
 }
 
-int vfgs_hip_add_grain_frames_dev(void* dY, void* dU, void* dV, unsigned width, unsigned height, unsigned stride,
-                                  unsigned cstride, unsigned nframes, uint64_t y_frame_pitch_bytes,
-                                  uint64_t c_frame_pitch_bytes, void* stream)
+static int check_frame_pitches(uint64_t ypitch, uint64_t cpitch)
 {
-	std::lock_guard<std::mutex> g(g_mu);
-	S().gen++;
-	if ((y_frame_pitch_bytes | c_frame_pitch_bytes) & 15) return fail(13, "frame pitches must be multiples of 16 bytes");
-	return run_device(dY, dU, dV, dY, dU, dV, width, 0, height, 0, height, stride, cstride, nframes,
-	                  y_frame_pitch_bytes, c_frame_pitch_bytes, pick_stream(stream));
+	if ((ypitch | cpitch) & 15) return fail(13, "frame pitches must be multiples of 16 bytes");
+	return 0;
 }
 
-int vfgs_hip_add_grain_frames_part_dev(void* dY, void* dU, void* dV, unsigned width, unsigned frame_height,
-                                       unsigned part_y, unsigned part_height, unsigned stride, unsigned cstride,
-                                       unsigned nframes, uint64_t y_frame_pitch_bytes, uint64_t c_frame_pitch_bytes,
-                                       void* stream)
+// what every call with a semi-planar side refuses for it; who: "semi-planar frames", "semi-planar frames with models", "planar to semi-planar"
+static int check_semiplanar(const char* who, const State& s, unsigned sample_shift, unsigned width)
 {
-	std::lock_guard<std::mutex> g(g_mu);
-	S().gen++;
-	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
-	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
-	if ((y_frame_pitch_bytes | c_frame_pitch_bytes) & 15) return fail(13, "frame pitches must be multiples of 16 bytes");
-	return run_device(dY, dU, dV, dY, dU, dV, width, 0, frame_height, part_y, part_height, stride, cstride, nframes,
-	                  y_frame_pitch_bytes, c_frame_pitch_bytes, pick_stream(stream));
+	if (s.csubx != 2)
+		return fail(40, "%s: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", who, s.csubx);
+	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
+		return fail(40, "%s: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", who, sample_shift, 8 + s.bs);
+	if (width > (unsigned)vfgs::kTileBlocks * 16)
+		return fail(40, "%s: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", who, width, vfgs::kTileBlocks * 16);
+	return 0;
 }
 
-// Frames anywhere in device memory (vfgs_hip.h): validated as a whole before anything moves, then launched in chunks of
-// kListFrames frames whose plane pointers travel in the kernel arguments.
-static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, unsigned nframes, unsigned width, unsigned height,
-                          unsigned stride, unsigned cstride, hipStream_t stream, DstGeom dg, bool whole = true, unsigned part_y = 0, unsigned part_h = 0,
-                          bool seeded = false, const uint32_t* seeds = nullptr,     // seeded: frame f is the frame behind vfgs_set_seed(seeds[f])
-                          const int sp_shift = -1,     // >= 0: semi-planar frames, U == V == the UV plane of a frame and cstride its row (run_device)
-                          const vfgs_hip_model* const* models = nullptr,     // a live model of the programmed depth and chroma format per frame (vfgs_hip_add_grain_frame_list_models_dev)
-                          const std::function<int()>* late_checks = nullptr)  // what the entry refuses BEHIND the list checks (the semi-planar call with models: 40, then 41)
+// a live model of the programmed depth and chroma format per frame, and no chroma mix; who: "frame list with models", "semi-planar frames with models".
+// width: refused here, with the models' code, where rows of that width are walked in parts (the semi-planar call has refused them under ITS code: it passes 0)
+static int check_models(const char* who, const State& s, const vfgs_hip_model* const* models, unsigned nframes, unsigned width)
 {
-	const bool sp = sp_shift >= 0;
-	const bool p2sp = dg.p2sp;        // (planar source, semi-planar destination: dst[f].U == dst[f].V is the UV plane)
+	if (!models) return fail(41, "%s: null list of models for %u frames", who, nframes);
+	for (unsigned f = 0; f < nframes; f++)
+	{
+		const vfgs_hip_model* m = models[f];
+		if (!model_live(m)) return fail(41, "%s: the model of frame %u is %s", who, f, m ? "not a live model (released?)" : "null");
+		if (m->bs != s.bs || m->csubx != s.csubx || m->csuby != s.csuby)
+			return fail(41, "%s: the model of frame %u was captured at depth %d, chroma subsampling %d,%d; programmed: depth %d, %d,%d", who, f,
+			            8 + m->bs, m->csubx, m->csuby, 8 + s.bs, s.csubx, s.csuby);
+	}
+	if (width > (unsigned)vfgs::kTileBlocks * 16)
+		return fail(41, "%s: width %u, rows of more than %d samples are walked in parts and have no kernel with a model per frame", who, width, vfgs::kTileBlocks * 16);
+	if (mix_active())
+		return fail(41, "%s: a chroma mix is active; the mix is one per launch, not one per model (clear it, or grain such pictures with the calls that honour it)", who);
+	return 0;
+}
+
+// a list of semi-planar frames as a frame list whose U and V planes are the UV plane (check_list, run_device)
+static std::vector<vfgs_hip_frame_ptrs> three_planes(const vfgs_hip_sp_frame* frames, unsigned nframes)
+{
+	std::vector<vfgs_hip_frame_ptrs> l(nframes);
+	for (unsigned f = 0; f < nframes; f++) l[f] = vfgs_hip_frame_ptrs{frames[f].Y, frames[f].UV, frames[f].UV};
+	return l;
+}
+
+// Frames anywhere in device memory (vfgs_hip.h): validated as a whole before anything moves (check_list), then launched in chunks of
+// kListFrames frames whose plane pointers travel in the kernel arguments (launch_list).
+struct ListCall {
+	GrainCall call;                                    // everything but the planes, the frame count and the list of ONE launch, which launch_list fills in; seeds: those of frame 0
+	const vfgs_hip_frame_ptrs *src = nullptr, *dst = nullptr;     // (the same pointer: in place)
+	unsigned nframes = 0;
+	const vfgs_hip_model* const* models = nullptr;     // a live model of the programmed depth and chroma format per frame (check_models)
+	bool check_programmed_shift = true;                // false: the entries with models -- their scale shifts were checked at capture
+
+	// (made where the entry is done with what it refuses first: inside an overlap region pick_stream takes the region's next stream)
+	ListCall(const vfgs_hip_frame_ptrs* src_, const vfgs_hip_frame_ptrs* dst_, unsigned n, const uint32_t* seeds, void* stream, const GrainCall& geometry)
+	    : call(geometry), src(src_), dst(dst_), nframes(n)
+	{
+		call.seeds = seeds;
+		call.stream = pick_stream(stream);
+	}
+	ListCall& with(const vfgs_hip_model* const* m) { models = m; check_programmed_shift = false; return *this; }
+};
+
+// Validation only: changes no state.
+static int check_list(const ListCall& l)
+{
+	const GrainCall& g = l.call;
+	const vfgs_hip_frame_ptrs *src = l.src, *dst = l.dst;
+	const unsigned nframes = l.nframes, width = g.width, stride = g.stride, cstride = g.cstride, part_y = g.part_y, part_h = g.part_h;
+	const DstGeom& dg = g.dg;
+	const bool sp = g.surface == Surface::semiplanar, p2sp = g.surface == Surface::to_semiplanar;     // (p2sp: dst[f].U == dst[f].V is the UV plane)
 	const bool dgeo = dg.out8 || p2sp;
 	const int ncomp = sp ? 2 : 3;     // planes of a source frame ...
 	const int ncomp_d = (sp || p2sp) ? 2 : 3;     // ... and of a destination frame
-	if (whole) { part_y = 0; part_h = height; }
-	State& s = S();
-	if (int e = ensure_init(-1)) return e;
-	if (nframes == 0) return 0;
-	if (seeded && !seeds) return fail(39, "seeded frame list: null seeds for %u frames", nframes);
+	const State& s = S();
 	if (!src || !dst) return fail(18, "frame list: null list");
 	for (unsigned f = 0; f < nframes; f++)
 	{
 		if (!src[f].Y || !src[f].U || !src[f].V || !dst[f].Y || !dst[f].U || !dst[f].V) return fail(18, "frame list: frame %u has a null plane", f);
-		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride, !models && !late_checks)) return e;
+		if (int e = check_geometry(s, src[f].Y, src[f].U, src[f].V, width, stride, cstride, l.check_programmed_shift)) return e;
 		if ((((uintptr_t)dst[f].Y | (uintptr_t)dst[f].U | (uintptr_t)dst[f].V) & 15)) return fail(7, "plane pointers must be 16-byte aligned");
 	}
 	if (sp && cstride < (width + 15) / 16 * 16)
@@ -3095,19 +3215,30 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			}
 		}
 	}
-	if (late_checks)
-		if (int e = (*late_checks)()) return e;
-	if (models)
-	{
-		// (what run_device would only find behind the first launch of a list of several: refused here, before anything moves)
-		const uint64_t sz = s.bs ? 2 : 1, crows = ((uint64_t)height + s.csuby - 1) / s.csuby;
-		if ((uint64_t)height * stride * sz >= 0x80000000ull || crows * cstride * sz >= 0x80000000ull)
-			return fail(15, "a plane of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)std::max((uint64_t)height * stride * sz, crows * cstride * sz));
-	}
-	for (unsigned f0 = 0, n = 0; f0 < nframes; f0 += n)
+	return 0;
+}
+
+// (what run_device would only find behind the first launch of a list of several: refused before anything moves)
+static int check_models_window(const ListCall& l)
+{
+	const State& s = S();
+	const uint64_t height = l.call.frame_h, sz = s.bs ? 2 : 1, crows = (height + s.csuby - 1) / s.csuby;
+	const uint64_t ybytes = height * l.call.stride * sz, cbytes = crows * l.call.cstride * sz;
+	if (ybytes >= 0x80000000ull || cbytes >= 0x80000000ull)
+		return fail(15, "a plane of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)std::max(ybytes, cbytes));
+	return 0;
+}
+
+static int launch_list(ListCall& l)
+{
+	const vfgs_hip_frame_ptrs *src = l.src, *dst = l.dst;
+	const vfgs_hip_model* const* models = l.models;
+	const uint32_t* const seeds = l.call.seeds;
+	GrainCall& c = l.call;     // (the planes, the frame count and the list of each launch in turn)
+	for (unsigned f0 = 0, n = 0; f0 < l.nframes; f0 += n)
 	{
 		// one launch: kListFrames frames at most -- with a model per frame, a run of frames whose models share the form of their images
-		n = std::min<unsigned>(vfgs::kListFrames, nframes - f0);
+		n = std::min<unsigned>(vfgs::kListFrames, l.nframes - f0);
 		if (models)
 			for (unsigned k = 1; k < n; k++)
 				if (models[f0 + k]->one_y != models[f0]->one_y || models[f0 + k]->one_c != models[f0]->one_c) { n = k; break; }
@@ -3124,17 +3255,79 @@ static int run_frame_list(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_p
 			for (unsigned k = 0; k < n; k++)
 			{
 				vfgs_hip_model* m = const_cast<vfgs_hip_model*>(models[f0 + k]);
-				HIP_TRY(m->guard.use(stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
+				HIP_TRY(m->guard.use(c.stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
 				ft.model[k] = m->dev;
 			}
 			mr.one_y = models[f0]->one_y; mr.one_c = models[f0]->one_c;
 			mr.first = models[f0]->rec;
+			c.mr = &mr;
 		}
-		if (int e = run_device(src[f0].Y, src[f0].U, src[f0].V, dst[f0].Y, dst[f0].U, dst[f0].V, width, 0, height, part_y, part_h, stride, cstride,
-		                       n, 0, 0, stream, dg, &ft, seeded ? seeds + f0 : nullptr, sp_shift, models ? &mr : nullptr))
-			return e;
+		c.copy(src[f0].Y, src[f0].U, src[f0].V, dst[f0].Y, dst[f0].U, dst[f0].V);
+		c.nframes = n;
+		c.list = &ft;
+		c.seeds = seeds ? seeds + f0 : nullptr;
+		if (int e = run_device(c)) return e;
 	}
 	return 0;
+}
+
+// a frame list with nothing of its own to refuse between the checks and the launches; needs_seeds: the entry takes a seed per frame and no null pointer for them
+static int run_list(ListCall l, bool needs_seeds = false)
+{
+	if (int e = ensure_init(-1)) return e;
+	if (l.nframes == 0) return 0;
+	if (needs_seeds && !l.call.seeds) return fail(39, "seeded frame list: null seeds for %u frames", l.nframes);
+	if (int e = check_list(l)) return e;
+	return launch_list(l);
+}
+
+int vfgs_hip_add_grain_stripe_dev(void* dY, void* dU, void* dV, unsigned y, unsigned width, unsigned height,
+                                  unsigned stride, unsigned cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	return run_device(GrainCall().in_place(dY, dU, dV).rows(width, stride, cstride).part(height, y, height, y).on(pick_stream(stream)));
+}
+
+int vfgs_hip_add_grain_frame_dev(void* dY, void* dU, void* dV, unsigned width, unsigned height,
+                                 unsigned stride, unsigned cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	return run_device(GrainCall().in_place(dY, dU, dV).rows(width, stride, cstride).whole(height).on(pick_stream(stream)));
+}
+
+int vfgs_hip_add_grain_frame_part_dev(void* dY, void* dU, void* dV, unsigned width, unsigned frame_height,
+                                      unsigned part_y, unsigned part_height, unsigned stride, unsigned cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	if (int e = check_part(part_y, part_height, frame_height)) return e;
+	return run_device(GrainCall().in_place(dY, dU, dV).rows(width, stride, cstride).part(frame_height, part_y, part_height).on(pick_stream(stream)));
+}
+
+int vfgs_hip_add_grain_frames_dev(void* dY, void* dU, void* dV, unsigned width, unsigned height, unsigned stride,
+                                  unsigned cstride, unsigned nframes, uint64_t y_frame_pitch_bytes,
+                                  uint64_t c_frame_pitch_bytes, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	if (int e = check_frame_pitches(y_frame_pitch_bytes, c_frame_pitch_bytes)) return e;
+	return run_device(GrainCall().in_place(dY, dU, dV).rows(width, stride, cstride).whole(height).frames(nframes, y_frame_pitch_bytes, c_frame_pitch_bytes)
+	                      .on(pick_stream(stream)));
+}
+
+int vfgs_hip_add_grain_frames_part_dev(void* dY, void* dU, void* dV, unsigned width, unsigned frame_height,
+                                       unsigned part_y, unsigned part_height, unsigned stride, unsigned cstride,
+                                       unsigned nframes, uint64_t y_frame_pitch_bytes, uint64_t c_frame_pitch_bytes,
+                                       void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	S().gen++;
+	if (int e = check_part(part_y, part_height, frame_height)) return e;
+	if (int e = check_frame_pitches(y_frame_pitch_bytes, c_frame_pitch_bytes)) return e;
+	return run_device(GrainCall().in_place(dY, dU, dV).rows(width, stride, cstride).part(frame_height, part_y, part_height)
+	                      .frames(nframes, y_frame_pitch_bytes, c_frame_pitch_bytes).on(pick_stream(stream)));
 }
 
 int vfgs_hip_add_grain_frame_list_dev(const vfgs_hip_frame_ptrs* frames, unsigned nframes, unsigned width, unsigned height,
@@ -3142,7 +3335,7 @@ int vfgs_hip_add_grain_frame_list_dev(const vfgs_hip_frame_ptrs* frames, unsigne
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	return run_frame_list(frames, frames, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom());
+	return run_list(ListCall(frames, frames, nframes, nullptr, stream, GrainCall().rows(width, stride, cstride).whole(height)));
 }
 
 int vfgs_hip_add_grain_frame_list_part_dev(const vfgs_hip_frame_ptrs* frames, unsigned nframes, unsigned width, unsigned frame_height,
@@ -3150,9 +3343,8 @@ int vfgs_hip_add_grain_frame_list_part_dev(const vfgs_hip_frame_ptrs* frames, un
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
-	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
-	return run_frame_list(frames, frames, nframes, width, frame_height, stride, cstride, pick_stream(stream), DstGeom(), false, part_y, part_height);
+	if (int e = check_part(part_y, part_height, frame_height)) return e;
+	return run_list(ListCall(frames, frames, nframes, nullptr, stream, GrainCall().rows(width, stride, cstride).part(frame_height, part_y, part_height)));
 }
 
 int vfgs_hip_add_grain_frame_list_copy_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, unsigned nframes, unsigned width,
@@ -3160,7 +3352,7 @@ int vfgs_hip_add_grain_frame_list_copy_dev(const vfgs_hip_frame_ptrs* src, const
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom());
+	return run_list(ListCall(src, dst, nframes, nullptr, stream, GrainCall().rows(width, stride, cstride).whole(height)));
 }
 
 int vfgs_hip_add_grain_frame_list_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, unsigned nframes, unsigned width,
@@ -3169,10 +3361,7 @@ int vfgs_hip_add_grain_frame_list_copy8_dev(const vfgs_hip_frame_ptrs* src, cons
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	DstGeom dg;
-	dg.out8 = true;
-	dg.stride = dst_stride; dg.cstride = dst_cstride;
-	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), dg);
+	return run_list(ListCall(src, dst, nframes, nullptr, stream, GrainCall().rows(width, stride, cstride).whole(height).dst_rows(true, dst_stride, dst_cstride)));
 }
 
 int vfgs_hip_add_grain_frame_list_seeded_dev(const vfgs_hip_frame_ptrs* frames, const uint32_t* seeds, unsigned nframes, unsigned width,
@@ -3180,7 +3369,7 @@ int vfgs_hip_add_grain_frame_list_seeded_dev(const vfgs_hip_frame_ptrs* frames, 
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	return run_frame_list(frames, frames, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom(), true, 0, 0, true, seeds);
+	return run_list(ListCall(frames, frames, nframes, seeds, stream, GrainCall().rows(width, stride, cstride).whole(height)), true);
 }
 
 int vfgs_hip_add_grain_frame_list_seeded_part_dev(const vfgs_hip_frame_ptrs* frames, const uint32_t* seeds, unsigned nframes, unsigned width,
@@ -3189,10 +3378,8 @@ int vfgs_hip_add_grain_frame_list_seeded_part_dev(const vfgs_hip_frame_ptrs* fra
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
-	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
-	return run_frame_list(frames, frames, nframes, width, frame_height, stride, cstride, pick_stream(stream), DstGeom(), false, part_y, part_height,
-	                      true, seeds);
+	if (int e = check_part(part_y, part_height, frame_height)) return e;
+	return run_list(ListCall(frames, frames, nframes, seeds, stream, GrainCall().rows(width, stride, cstride).part(frame_height, part_y, part_height)), true);
 }
 
 int vfgs_hip_add_grain_frame_list_seeded_copy_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
@@ -3201,7 +3388,7 @@ int vfgs_hip_add_grain_frame_list_seeded_copy_dev(const vfgs_hip_frame_ptrs* src
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom(), true, 0, 0, true, seeds);
+	return run_list(ListCall(src, dst, nframes, seeds, stream, GrainCall().rows(width, stride, cstride).whole(height)), true);
 }
 
 int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds,
@@ -3210,10 +3397,7 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	DstGeom dg;
-	dg.out8 = true;
-	dg.stride = dst_stride; dg.cstride = dst_cstride;
-	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), dg, true, 0, 0, true, seeds);
+	return run_list(ListCall(src, dst, nframes, seeds, stream, GrainCall().rows(width, stride, cstride).whole(height).dst_rows(true, dst_stride, dst_cstride)), true);
 }
 
 // Models as objects (vfgs_hip.h).  Capture builds the image upload_tables would build for ordinary rows -- same form, same bytes, device-generated
@@ -3322,24 +3506,15 @@ int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, con
 	s.gen++;
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
-	if (!models) return fail(41, "frame list with models: null list of models for %u frames", nframes);
-	for (unsigned f = 0; f < nframes; f++)
-	{
-		const vfgs_hip_model* m = models[f];
-		if (!model_live(m)) return fail(41, "frame list with models: the model of frame %u is %s", f, m ? "not a live model (released?)" : "null");
-		if (m->bs != s.bs || m->csubx != s.csubx || m->csuby != s.csuby)
-			return fail(41, "frame list with models: the model of frame %u was captured at depth %d, chroma subsampling %d,%d; programmed: depth %d, %d,%d", f,
-			            8 + m->bs, m->csubx, m->csuby, 8 + s.bs, s.csubx, s.csuby);
-	}
-	if (width > (unsigned)vfgs::kTileBlocks * 16)
-		return fail(41, "frame list with models: width %u, rows of more than %d samples are walked in parts and have no kernel with a model per frame", width, vfgs::kTileBlocks * 16);
-	if (mix_active())
-		return fail(41, "frame list with models: a chroma mix is active; the mix is one per launch, not one per model (clear it, or grain such pictures with the calls that honour it)");
-	return run_frame_list(src, dst, nframes, width, height, stride, cstride, pick_stream(stream), DstGeom(), true, 0, 0, seeds != nullptr, seeds, -1, models);
+	if (int e = check_models("frame list with models", s, models, nframes, width)) return e;
+	ListCall l = ListCall(src, dst, nframes, seeds, stream, GrainCall().rows(width, stride, cstride).whole(height)).with(models);
+	if (int e = check_list(l)) return e;
+	if (int e = check_models_window(l)) return e;
+	return launch_list(l);
 }
 
 // Semi-planar frames (vfgs_hip.h): a luma plane and ONE plane of interleaved Cb/Cr pairs per frame.  What this call alone refuses is
-// refused here, before anything moves; the list then is a frame list whose U and V planes are the UV plane (run_frame_list, run_device).
+// refused here, before anything moves; the list then is a frame list whose U and V planes are the UV plane (check_list, run_device).
 int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
                                          unsigned width, unsigned height, unsigned stride, unsigned uv_stride, unsigned sample_shift, void* stream)
 {
@@ -3348,30 +3523,20 @@ int vfgs_hip_add_grain_sp_frame_list_dev(const vfgs_hip_sp_frame* src, const vfg
 	s.gen++;
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
-	if (s.csubx != 2)
-		return fail(40, "semi-planar frames: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
-	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
-		return fail(40, "semi-planar frames: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
-	if (width > (unsigned)vfgs::kTileBlocks * 16)
-		return fail(40, "semi-planar frames: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
+	if (int e = check_semiplanar("semi-planar frames", s, sample_shift, width)) return e;
 	// (an active mix is honoured for all-one-pattern models at 8 and 10 bit; a general-form model under a mix is refused in run_device, where
 	// the form of the table image is known, with this code and before any state moves)
 	if (mix_active() && s.bs == 4)
 		return fail(40, "semi-planar frames: a chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit");
 	if (!src || !dst) return fail(18, "frame list: null list");
-	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd;
-	for (unsigned f = 0; f < nframes; f++) ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};
-	if (src != dst)
-	{
-		pd.resize(nframes);
-		for (unsigned f = 0; f < nframes; f++) pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
-	}
-	return run_frame_list(ps.data(), src != dst ? pd.data() : ps.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), DstGeom(), true, 0, 0,
-	                      seeds != nullptr, seeds, (int)sample_shift);
+	const std::vector<vfgs_hip_frame_ptrs> ps = three_planes(src, nframes), pd = three_planes(dst, src != dst ? nframes : 0);
+	ListCall l(ps.data(), src != dst ? pd.data() : ps.data(), nframes, seeds, stream, GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::semiplanar, sample_shift));     // (one list where the caller's are one: check_list's src != dst)
+	if (int e = check_list(l)) return e;
+	return launch_list(l);
 }
 
 // ... with a model per frame (vfgs_hip.h): the list checks of the call above, then its refusals (40), then those of the planar call with models
-// (41); then a frame list that is both (run_frame_list cuts it into runs of one form, run_device takes sp_shift and the ModelRun together).
+// (41); then a frame list that is both (launch_list cuts it into runs of one form, run_device takes the surface and the ModelRun together).
 int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst, const vfgs_hip_model* const* models,
                                                 const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
                                                 unsigned uv_stride, unsigned sample_shift, void* stream)
@@ -3382,35 +3547,13 @@ int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, co
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
 	if (!src || !dst) return fail(18, "frame list: null list");
-	const std::function<int()> late = [&]() -> int {
-		if (s.csubx != 2)
-			return fail(40, "semi-planar frames with models: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
-		if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
-			return fail(40, "semi-planar frames with models: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
-		if (width > (unsigned)vfgs::kTileBlocks * 16)
-			return fail(40, "semi-planar frames with models: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
-		if (!models) return fail(41, "semi-planar frames with models: null list of models for %u frames", nframes);
-		for (unsigned f = 0; f < nframes; f++)
-		{
-			const vfgs_hip_model* m = models[f];
-			if (!model_live(m)) return fail(41, "semi-planar frames with models: the model of frame %u is %s", f, m ? "not a live model (released?)" : "null");
-			if (m->bs != s.bs || m->csubx != s.csubx || m->csuby != s.csuby)
-				return fail(41, "semi-planar frames with models: the model of frame %u was captured at depth %d, chroma subsampling %d,%d; programmed: depth %d, %d,%d", f,
-				            8 + m->bs, m->csubx, m->csuby, 8 + s.bs, s.csubx, s.csuby);
-		}
-		if (mix_active())
-			return fail(41, "semi-planar frames with models: a chroma mix is active; the mix is one per launch, not one per model (clear it, or grain such pictures with the calls that honour it)");
-		return 0;
-	};
-	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd;
-	for (unsigned f = 0; f < nframes; f++) ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};
-	if (src != dst)
-	{
-		pd.resize(nframes);
-		for (unsigned f = 0; f < nframes; f++) pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
-	}
-	return run_frame_list(ps.data(), src != dst ? pd.data() : ps.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), DstGeom(), true, 0, 0,
-	                      seeds != nullptr, seeds, (int)sample_shift, models, &late);
+	const std::vector<vfgs_hip_frame_ptrs> ps = three_planes(src, nframes), pd = three_planes(dst, src != dst ? nframes : 0);
+	ListCall l = ListCall(ps.data(), src != dst ? pd.data() : ps.data(), nframes, seeds, stream, GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::semiplanar, sample_shift)).with(models);
+	if (int e = check_list(l)) return e;
+	if (int e = check_semiplanar("semi-planar frames with models", s, sample_shift, width)) return e;
+	if (int e = check_models("semi-planar frames with models", s, models, nframes, 0)) return e;
+	if (int e = check_models_window(l)) return e;
+	return launch_list(l);
 }
 
 // ... with the narrowed 8-bit destination (P010 / P210 / P012 in, NV12 / NV16 out): the call above with a destination geometry of its own.
@@ -3424,12 +3567,7 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
 	s.gen++;
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
-	if (s.csubx != 2)
-		return fail(40, "semi-planar frames: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
-	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
-		return fail(40, "semi-planar frames: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
-	if (width > (unsigned)vfgs::kTileBlocks * 16)
-		return fail(40, "semi-planar frames: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
+	if (int e = check_semiplanar("semi-planar frames", s, sample_shift, width)) return e;
 	if (s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
 	if (mix_active())
 		return fail(40, "semi-planar frames: a chroma mix is active and the destination is narrowed to 8 bit: the kernels of the mix have no such form");
@@ -3438,52 +3576,35 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
 	const unsigned nb16 = (width + 15) / 16 * 16;
 	if (dst_stride < nb16 || dst_uv_stride < nb16) return fail(6, "destination stride too small");
 	if (dst_stride % 16 || dst_uv_stride % 16) return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
-	std::vector<vfgs_hip_frame_ptrs> ps(nframes), pd(nframes);
-	for (unsigned f = 0; f < nframes; f++)
-	{
-		ps[f] = vfgs_hip_frame_ptrs{src[f].Y, src[f].UV, src[f].UV};
-		pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
-	}
-	DstGeom dg;
-	dg.out8 = true;
-	dg.stride = dst_stride; dg.cstride = dst_uv_stride;
-	return run_frame_list(ps.data(), pd.data(), nframes, width, height, stride, uv_stride, pick_stream(stream), dg, true, 0, 0, seeds != nullptr, seeds,
-	                      (int)sample_shift);
+	const std::vector<vfgs_hip_frame_ptrs> ps = three_planes(src, nframes), pd = three_planes(dst, nframes);
+	ListCall l(ps.data(), pd.data(), nframes, seeds, stream, GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::semiplanar, sample_shift).dst_rows(true, dst_stride, dst_uv_stride));
+	if (int e = check_list(l)) return e;
+	return launch_list(l);
 }
 
 // A planar source, a semi-planar destination (vfgs_hip.h): what a software decoder hands out goes onto the surface a display takes.  The planar
 // list call with a destination geometry of its own whose U and V planes are the UV plane; what the semi-planar calls refuse for their
 // destination is refused here with their codes, before anything moves.
-static int run_to_sp(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height,
-                     unsigned stride, unsigned cstride, unsigned dst_stride, unsigned dst_uv_stride, unsigned sample_shift, bool out8, void* stream)
+static int run_to_sp(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes, const GrainCall& c, void* stream)
 {
 	State& s = S();
 	s.gen++;
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
-	if (s.csubx != 2)
-		return fail(40, "planar to semi-planar: the chroma format has csubx %d, the interleaved plane exists at 4:2:0 and 4:2:2 (csubx 2)", s.csubx);
-	if (sample_shift != 0 && (s.bs == 0 || sample_shift != 8u - (unsigned)s.bs))
-		return fail(40, "planar to semi-planar: sample_shift %u at depth %d (0, or 16 - depth with 16-bit containers)", sample_shift, 8 + s.bs);
-	if (width > (unsigned)vfgs::kTileBlocks * 16)
-		return fail(40, "planar to semi-planar: width %u, rows of more than %d samples are walked in parts and have no semi-planar kernel", width, vfgs::kTileBlocks * 16);
-	if (out8 && s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
+	if (int e = check_semiplanar("planar to semi-planar", s, c.sample_shift, c.width)) return e;
+	if (c.dg.out8 && s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
 	if (mix_active())
 		return fail(40, "planar to semi-planar: a chroma mix is active; these kernels have no form with the luma over their chroma rows (grain planar with the mix calls)");
 	if (!src || !dst) return fail(18, "frame list: null list");
 	// (the destination's pitches, with the codes of the calls it is carried over from: a UV row is as many containers as the luma row)
-	const unsigned nb16 = (width + 15) / 16 * 16, dsz = (out8 || s.bs == 0) ? 1 : 2;
-	if (dst_stride < nb16 || dst_uv_stride < nb16)
-		return fail(6, "destination stride %u/%u too small: whole 16-sample blocks are written (need >= %u/%u)", dst_stride, dst_uv_stride, nb16, nb16);
-	if ((dst_stride * dsz) % 16 || (dst_uv_stride * dsz) % 16) return fail(8, "destination row pitches must be multiples of 16 bytes");
-	std::vector<vfgs_hip_frame_ptrs> ps(src, src + nframes), pd(nframes);
-	for (unsigned f = 0; f < nframes; f++) pd[f] = vfgs_hip_frame_ptrs{dst[f].Y, dst[f].UV, dst[f].UV};
-	DstGeom dg;
-	dg.out8 = out8;
-	dg.p2sp = true;
-	dg.p2sp_shift = sample_shift;
-	dg.stride = dst_stride; dg.cstride = dst_uv_stride;
-	return run_frame_list(ps.data(), pd.data(), nframes, width, height, stride, cstride, pick_stream(stream), dg, true, 0, 0, seeds != nullptr, seeds);
+	const unsigned nb16 = (c.width + 15) / 16 * 16, dsz = (c.dg.out8 || s.bs == 0) ? 1 : 2;
+	if (c.dg.stride < nb16 || c.dg.cstride < nb16)
+		return fail(6, "destination stride %u/%u too small: whole 16-sample blocks are written (need >= %u/%u)", c.dg.stride, c.dg.cstride, nb16, nb16);
+	if ((c.dg.stride * dsz) % 16 || (c.dg.cstride * dsz) % 16) return fail(8, "destination row pitches must be multiples of 16 bytes");
+	const std::vector<vfgs_hip_frame_ptrs> pd = three_planes(dst, nframes);
+	ListCall l(src, pd.data(), nframes, seeds, stream, c);
+	if (int e = check_list(l)) return e;
+	return launch_list(l);
 }
 
 int vfgs_hip_add_grain_frame_list_to_sp_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
@@ -3491,7 +3612,7 @@ int vfgs_hip_add_grain_frame_list_to_sp_dev(const vfgs_hip_frame_ptrs* src, cons
                                             unsigned dst_uv_stride, unsigned sample_shift, void* stream)
 {
 	std::lock_guard<std::mutex> g(g_mu);
-	return run_to_sp(src, dst, seeds, nframes, width, height, stride, cstride, dst_stride, dst_uv_stride, sample_shift, false, stream);
+	return run_to_sp(src, dst, seeds, nframes, GrainCall().rows(width, stride, cstride).whole(height).to(Surface::to_semiplanar, sample_shift).dst_rows(false, dst_stride, dst_uv_stride), stream);
 }
 
 int vfgs_hip_add_grain_frame_list_to_sp8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes,
@@ -3499,7 +3620,7 @@ int vfgs_hip_add_grain_frame_list_to_sp8_dev(const vfgs_hip_frame_ptrs* src, con
                                              unsigned dst_uv_stride, void* stream)
 {
 	std::lock_guard<std::mutex> g(g_mu);
-	return run_to_sp(src, dst, seeds, nframes, width, height, stride, cstride, dst_stride, dst_uv_stride, 0, true, stream);
+	return run_to_sp(src, dst, seeds, nframes, GrainCall().rows(width, stride, cstride).whole(height).to(Surface::to_semiplanar, 0).dst_rows(true, dst_stride, dst_uv_stride), stream);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,
@@ -3533,11 +3654,10 @@ int vfgs_hip_add_grain_copy_dev(const void* sY, const void* sU, const void* sV, 
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
-	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
-	if ((y_frame_pitch_bytes | c_frame_pitch_bytes) & 15) return fail(13, "frame pitches must be multiples of 16 bytes");
-	return run_device(sY, sU, sV, dY, dU, dV, width, 0, frame_height, part_y, part_height, stride, cstride, nframes,
-	                  y_frame_pitch_bytes, c_frame_pitch_bytes, pick_stream(stream));
+	if (int e = check_part(part_y, part_height, frame_height)) return e;
+	if (int e = check_frame_pitches(y_frame_pitch_bytes, c_frame_pitch_bytes)) return e;
+	return run_device(GrainCall().copy(sY, sU, sV, dY, dU, dV).rows(width, stride, cstride).part(frame_height, part_y, part_height)
+	                      .frames(nframes, y_frame_pitch_bytes, c_frame_pitch_bytes).on(pick_stream(stream)));
 }
 
 int vfgs_hip_add_grain_copy8_dev(const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV,
@@ -3548,15 +3668,11 @@ int vfgs_hip_add_grain_copy8_dev(const void* sY, const void* sU, const void* sV,
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	S().gen++;
-	if (part_y & 15) return fail(11, "part_y must be a multiple of 16");
-	if (part_y > frame_height || part_height > frame_height - part_y) return fail(12, "part exceeds the frame");     // (no 32-bit wrap)
-	if ((y_frame_pitch_bytes | c_frame_pitch_bytes) & 15) return fail(13, "frame pitches must be multiples of 16 bytes");
-	DstGeom dg;
-	dg.out8 = true;
-	dg.stride = dst_stride; dg.cstride = dst_cstride;
-	dg.ypitch = dst_y_frame_pitch_bytes; dg.cpitch = dst_c_frame_pitch_bytes;
-	return run_device(sY, sU, sV, dY, dU, dV, width, 0, frame_height, part_y, part_height, stride, cstride, nframes,
-	                  y_frame_pitch_bytes, c_frame_pitch_bytes, pick_stream(stream), dg);
+	if (int e = check_part(part_y, part_height, frame_height)) return e;
+	if (int e = check_frame_pitches(y_frame_pitch_bytes, c_frame_pitch_bytes)) return e;
+	return run_device(GrainCall().copy(sY, sU, sV, dY, dU, dV).rows(width, stride, cstride).part(frame_height, part_y, part_height)
+	                      .frames(nframes, y_frame_pitch_bytes, c_frame_pitch_bytes).dst_rows(true, dst_stride, dst_cstride, dst_y_frame_pitch_bytes, dst_c_frame_pitch_bytes)
+	                      .on(pick_stream(stream)));
 }
 
 void vfgs_hip_get_seed_state(uint32_t out[4])
