@@ -304,9 +304,11 @@ namespace vfgs {
 
 ImageLayout layout_of(int csubx, int csuby, bool oney, bool onec, bool depth8) { return image_layout(csubx, csuby, oney, onec, depth8); }
 
-void describe_launch(char* out, size_t n, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist)
+// (the kernels of the row walk are named as this model of them; every other family as the product names it)
+void name_launch(const KernelKey& k, char* out, size_t n)
 {
-	snprintf(out, n, "stub<%d,%d,%d,%d,%d,%d,%d,%d>", depth, csubx, csuby, out8, oney, onec, wide, persist);
+	if (k.family == Family::rw) snprintf(out, n, "stub<%d,%d,%d,%d,%d,%d,%d,%d>", k.depth, k.csubx, k.csuby, k.out8, k.oney, k.onec, k.wide, k.persist);
+	else kernel_name(k, out, n);
 }
 
 static unsigned char g_sink;
@@ -319,9 +321,10 @@ static void touch(const void* p, size_t n)
 	g_sink ^= x;
 }
 
-hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist,
-                        int grid, hipStream_t stream)
+hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, const KernelKey& key, int grid, hipStream_t stream)
 {
+	const int depth = key.depth, csubx = key.csubx, csuby = key.csuby;
+	const bool out8 = key.out8, oney = key.oney, onec = key.onec, wide = key.wide, persist = key.persist;
 	if ((out8 && depth != 10) || wide != (a.nblk > kTileBlocks) || grid <= 0) return hipErrorInvalidValue;
 	if ((a.listed != 0) != (list != nullptr) || (list && a.nframes > kListFrames)) return hipErrorInvalidValue;
 	if (persist && (oney || wide || depth != 10)) return hipErrorInvalidValue;

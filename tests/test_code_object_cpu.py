@@ -70,7 +70,7 @@ def grain_kernels(tmp_path_factory):
 
 
 def test_every_instantiation_is_in_the_library(grain_kernels):
-    # 64 at 10 bit (with the narrowed destination), 24 at 8 bit: the dispatcher's table (vfgs_kernel.hip launch_depth)
+    # 64 at 10 bit (with the narrowed destination), 24 at 8 bit: the dispatcher's table (vfgs_layout.h kernel_exists)
     assert len([k for k in grain_kernels if k[0] == 10]) == 64 and len([k for k in grain_kernels if k[0] == 8]) == 24
 
 

@@ -65,9 +65,7 @@ def check_models(ms):
 
 
 def kernel_of(ms, k):
-    oy, oc = ms.forms[k]
-    b = lambda v: "true" if v else "false"
-    return f"grain_ml_kernel<{ms.depth},{ms.sx},{ms.sy},{b(oy)},{b(oc)}>"
+    return T.kernel_name("grain_ml_kernel", ms.depth, ms.sx, ms.sy, *ms.forms[k])
 
 
 def run_list(hip, ms, pick, w, seeded, tag, out_of_place=False):

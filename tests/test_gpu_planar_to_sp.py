@@ -49,10 +49,6 @@ def hip():
     h.lib.vfgs_hip_reset_state()
 
 
-def one(v):
-    return "true" if v else "false"
-
-
 def mk(n, w, h, depth, sy, seed):
     return [garbage_frame(w, h, depth, 2, sy, seed + i) for i in range(n)]
 
@@ -107,7 +103,7 @@ def run(hip, ora, frames, shift=0, out8=False, seeds=None, pad=16, uv_pad=48, sh
 
 
 def kernel_name(info, out8):
-    return f"{'grain_p2sp8_kernel' if out8 else 'grain_p2sp_kernel'}<{info['depth']},{info['csuby']},{one(info['one_y'])},{one(info['one_c'])}>"
+    return T.kernel_name("grain_p2sp8_kernel" if out8 else "grain_p2sp_kernel", info["depth"], info["csuby"], info["one_y"], info["one_c"])
 
 
 def assert_launch(info, out8, depth, nframes):

@@ -105,7 +105,7 @@ def test_widest_row_of_the_parameter_table_and_one_block_more(hip, width, parts)
 WIDE_FORMATS = ["fgs_sei_10_420", "fgs_afgs1_test1_8_420", "fgs_sei_8_420", "fgs_afgs1_test1_8_444", "fgs_sei_10_422", "fgs_sei_10_444",
                 "fgs_sei_ff_test6_10_440", "fgs_sei_ar_test1_10_420", "fgs_afgs1_test1_10_444", "fgs_sei_ff_test6_10_444", "fgs_afgs1_test3_10_422"]
 # the form of the table image a wide picture gets (luma, chroma): at 4:2:0 and 4:4:4 one-pattern chroma keeps its form, and luma under
-# it; every other case falls back to the general form (vfgs_host.cpp image_form, vfgs_kernel.hip launch_form)
+# it; every other case falls back to the general form (vfgs_host.cpp image_form, vfgs_layout.h kernel_exists)
 WIDE_FORM = {"fgs_sei_10_420": (0, 1), "fgs_afgs1_test1_8_420": (1, 1), "fgs_sei_8_420": (0, 1), "fgs_afgs1_test1_8_444": (1, 1), "fgs_sei_10_422": (0, 0),
              "fgs_sei_10_444": (0, 1), "fgs_sei_ff_test6_10_440": (0, 0), "fgs_sei_ar_test1_10_420": (1, 1), "fgs_afgs1_test1_10_444": (1, 1),
              "fgs_sei_ff_test6_10_444": (0, 0), "fgs_afgs1_test3_10_422": (0, 0)}

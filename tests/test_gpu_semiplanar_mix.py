@@ -160,7 +160,7 @@ def launches(hip):
 
 
 def kernel_name(c):
-    return f"grain_sp_mix_kernel<{c['depth']},{c['suby']}>"
+    return T.kernel_name("grain_sp_mix_kernel", c["depth"], c["suby"])
 
 
 def check(devs, res, what=""):

@@ -55,8 +55,7 @@ class Models:
         return [SP.garbage_sp_frame(w, h, self.depth, self.sy, shift, seed + i) for i in range(n)]
 
     def kernel(self, k):
-        b = lambda v: "true" if v else "false"
-        return f"grain_spml_kernel<{self.depth},{self.sy},{b(self.forms[k][0])},{b(self.forms[k][1])}>"
+        return T.kernel_name("grain_spml_kernel", self.depth, self.sy, *self.forms[k])
 
 
 def fresh_seeds(n, seed):

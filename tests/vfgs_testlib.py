@@ -118,6 +118,14 @@ def trace_geometry(records):
     return depth, subx, suby
 
 
+def kernel_name(kernel, *args):
+    """The kernel a launch record names (last_launch_info()["kernel"]; csrc/vfgs_layout.h kernel_name): the template arguments in the kernel's
+    order -- the depth and the chroma subsampling factors first, as numbers; the rest, bools or the record's 0 / 1, as true / false.
+    kernel_name("grain_sp_kernel", 10, 2, True, 0) -> "grain_sp_kernel<10,2,true,false>"."""
+    first = 3 if kernel in ("grain_rw_kernel", "grain_ml_kernel", "grain_mix_kernel") else 2      # depth, csubx, csuby / depth, csuby
+    return f"{kernel}<{','.join(str(int(a)) if i < first else ('true' if a else 'false') for i, a in enumerate(args))}>"
+
+
 # --------------------------------------------------------------------------- frames
 
 class Frame:

@@ -28,9 +28,9 @@
 #include "vfgs_layout.h"
 
 namespace vfgs {
-hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream);
+hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream);
 ImageLayout layout_of(int csubx, int csuby, bool oney, bool onec, bool depth8);
-void describe_launch(char* out, size_t n, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist);
+void name_launch(const KernelKey& k, char* out, size_t n);
 hipError_t launch_fw_generate(const FwLaunch& L, hipStream_t stream);
 hipError_t launch_fw_patch(uint8_t* img, const int8_t* bank, uint32_t mask_luma, uint32_t mask_chroma, int csubx, int csuby,
                            bool one_y, bool one_c, int slot_y, int slot_cb, int slot_cr, bool depth8, hipStream_t stream);
@@ -1295,7 +1295,7 @@ int check_luts(State& s)
 
 // Which form of the table image (vfgs_layout.h) the current state gets.  wide: the picture is wider than 8192 samples (rows walked
 // in parts); those kernels exist for the combinations that matter there -- everything general, one-pattern chroma under general
-// or one-pattern luma, at 4:2:0 and 4:4:4 (vfgs_kernel.hip launch_form) -- and every other case gets the general form even where
+// or one-pattern luma, at 4:2:0 and 4:4:4 (vfgs_layout.h kernel_exists) -- and every other case gets the general form even where
 // one pattern would do.  The pattern LUTs must have been digested.
 void image_form(const State& s, bool wide, bool* one_y, bool* one_c)
 {
@@ -1548,6 +1548,7 @@ struct Launch : GrainCall {
 	uint64_t first_cur = 0, first_up = 0, second_cur = 0, lo = ~0ull, hi = 0;     // stream positions (plan_seeds)
 	bool stripes = false, persist = false;  // the stream comes as a StripeStream image; persistent luma workgroups
 	long per_frame = 0, grid = 0;
+	vfgs::KernelKey key{};                   // which kernel serves the call (launch)
 
 	Launch(State& state, const GrainCall& c) : GrainCall(c), s(state), sp(surface == Surface::semiplanar), p2sp(surface == Surface::to_semiplanar) {}
 	int admit();
@@ -1741,7 +1742,6 @@ int Launch::bind_tables()
 	if (mr)
 	{
 		// (the images are the models' own, made visible to `stream` by launch_list; the programmed state's image is neither built nor looked at)
-		a.models_kernel = 1;
 		a.tables = list->model[0] + vfgs::kModelRecordBytes;
 		a.lo2[0] = mr->first.lo2[0]; a.lo2[1] = mr->first.lo2[1]; a.hi2[0] = mr->first.hi2[0]; a.hi2[1] = mr->first.hi2[1];
 		a.pk_shift = mr->first.pk_shift;
@@ -1850,21 +1850,21 @@ int Launch::plan_grid()
 // The launch -- under a chroma mix over shared luma bytes, two of them.
 int Launch::launch()
 {
-	if (sp)
-	{
-		a.sp_kernel = 1;
-		a.sp_shift2 = sample_shift * 0x10001u;
-	}
-	if (p2sp)
-	{
-		a.sp_kernel = 2;
-		a.sp_shift2 = sample_shift * 0x10001u;
-	}
+	// the kernel of this call (vfgs_layout.h KernelKey), formed once: admit() has refused a model per frame under a mix, with a narrowed destination
+	// or from a planar source, and a planar source under a mix
+	using vfgs::Family;
+	key = vfgs::KernelKey{8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist,
+	                      p2sp ? (dg.out8 ? Family::p2sp8 : Family::p2sp)
+	                      : sp ? (mix ? Family::sp_mix : dg.out8 ? Family::sp8 : mr ? Family::spml : Family::sp)
+	                           : (mix ? Family::mix : mr ? Family::ml : Family::rw)};
+	if (mr && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
+	const vfgs::FamilyFields ff = vfgs::family_fields(key.family);
+	a.models_kernel = ff.models_kernel; a.mix_kernel = ff.mix_kernel; a.sp_kernel = ff.sp_kernel;
+	if (sp || p2sp) a.sp_shift2 = sample_shift * 0x10001u;
 	if (mix)
 	{
 		// (semi-planar frames: grain_sp_mix_kernel, whose UV workgroups read the luma over their rows; the same two-launch rule)
 		if (!(img_one_y && img_one_c) || persist) return fail(19, "internal: the table image is not the form the chroma mix was admitted for");
-		a.mix_kernel = 1;
 		a.mix_lw = (int)width;
 		for (int c = 0; c < 2; c++)
 		{
@@ -1887,11 +1887,11 @@ int Launch::launch()
 		if (shared)
 		{
 			a.mix_planes = 1;      // chroma planes only
-			HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, true, true, wide, false, (int)grid, stream));
+			HIP_TRY(vfgs::launch_grain(a, list, key, (int)grid, stream));
 			a.mix_planes = 2;      // luma only
 		}
 	}
-	HIP_TRY(vfgs::launch_grain(a, list, 8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist, (int)grid, stream));
+	HIP_TRY(vfgs::launch_grain(a, list, key, (int)grid, stream));
 	return 0;
 }
 
@@ -1920,39 +1920,10 @@ void Launch::record_launch()
 		li.parts_per_row = (int)nparts;
 		li.persistent_luma_workgroups = persist ? a.persist_wgs : 0;
 		li.waves_per_workgroup = vfgs::kWavesPerWG;
-		const vfgs::ImageLayout L = vfgs::layout_of(s.csubx, s.csuby, img_one_y, img_one_c, s.bs == 0);
-		li.lds_bytes_per_workgroup = vfgs::lds_allocation(s.bs != 0, img_one_y, img_one_c, wide, L.lds_bytes + vfgs::kParamBytes);     // (what the kernel allocates)
-		vfgs::describe_launch(li.kernel, sizeof li.kernel, 8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist);
-		if (mr)     // (a model per frame: depth, chroma subsampling x / y, one-pattern luma, one-pattern chroma; the LDS allocation of its grain_rw_kernel twin, above)
-			snprintf(li.kernel, sizeof li.kernel, "grain_ml_kernel<%d,%d,%d,%s,%s>", 8 + s.bs, s.csubx, s.csuby, img_one_y ? "true" : "false", img_one_c ? "true" : "false");
-		if (mix)
-		{
-			// (the kernels of the mix: depth, chroma subsampling x / y, 8-bit destination, rows walked in parts; `launches` counts both launches of an in-place call)
-			li.lds_bytes_per_workgroup = vfgs::mix_lds_allocation(L.lds_bytes + vfgs::kParamBytes);
-			snprintf(li.kernel, sizeof li.kernel, "grain_mix_kernel<%d,%d,%d,%s,%s>", 8 + s.bs, s.csubx, s.csuby, dg.out8 ? "true" : "false", wide ? "true" : "false");
-			if (a.mix_planes) li.launches++;
-		}
-		if (sp)
-		{
-			// (the kernels of semi-planar frames: depth, chroma subsampling y, one-pattern luma, one-pattern chroma; "chroma" in the per-plane figures is the UV plane)
-			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, img_one_c));
-			// (grain_sp8_kernel: the same family with the narrowed 8-bit destination; grain_spml_kernel: with a model per frame, the form is the models')
-			snprintf(li.kernel, sizeof li.kernel, "%s<%d,%d,%s,%s>", dg.out8 ? "grain_sp8_kernel" : (mr ? "grain_spml_kernel" : "grain_sp_kernel"), 8 + s.bs, s.csuby,
-			         img_one_y ? "true" : "false", img_one_c ? "true" : "false");
-			if (mix)
-			{
-				// (... under the mix: depth, chroma subsampling y; all-one-pattern images)
-				li.lds_bytes_per_workgroup = vfgs::sp_mix_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, true));
-				snprintf(li.kernel, sizeof li.kernel, "grain_sp_mix_kernel<%d,%d>", 8 + s.bs, s.csuby);
-			}
-		}
-		if (p2sp)
-		{
-			// (a planar source, a semi-planar destination: grain_sp_kernel's template arguments, residency and LDS allocation)
-			li.lds_bytes_per_workgroup = vfgs::sp_lds_allocation(vfgs::sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, s.img_one_c));
-			snprintf(li.kernel, sizeof li.kernel, "%s<%d,%d,%s,%s>", dg.out8 ? "grain_p2sp8_kernel" : "grain_p2sp_kernel", 8 + s.bs, s.csuby, s.img_one_y ? "true" : "false",
-			         s.img_one_c ? "true" : "false");
-		}
+		// (semi-planar frames: "chroma" in the per-plane figures is the UV plane)
+		li.lds_bytes_per_workgroup = vfgs::kernel_lds_bytes(key);     // (what the kernel allocates)
+		vfgs::name_launch(key, li.kernel, sizeof li.kernel);
+		if (mix && a.mix_planes) li.launches++;     // (`launches` counts both launches of an in-place call under the mix)
 		g_last_launch_valid = true;
 	}
 }

@@ -1931,284 +1931,137 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpMixWgPerCU) void grain_sp_mix_
 // ---------------------------------------------------------------------------------------
 // host-side launcher (called from vfgs_host.cpp)
 
-template <int DEPTH, int CSUBX, int CSUBY, bool OUT8>
-static hipError_t launch_mix(const KernelArgs& a, const FrameTable& ft, bool wide, int grid, hipStream_t stream)
+// What a launch's arguments must say for the kernel of key `k` (vfgs_layout.h KernelKey) to be the one that serves them; WHICH kernels exist
+// is not decided here (kernel_exists, at the leaf of the dispatch below).  The host refuses all of this before it gets here.
+static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const KernelKey& k)
 {
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts);
-	if (wide)
+	const Family f = k.family;
+	const FamilyFields ff = family_fields(f);
+	if (a.models_kernel != ff.models_kernel || a.mix_kernel != ff.mix_kernel || a.sp_kernel != ff.sp_kernel) return false;
+	if (k.wide != (a.nblk > kTileBlocks)) return false;
+	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return false;
+	if ((a.listed != 0) != (list != nullptr) || (list && a.nframes > kListFrames)) return false;
+	if (a.models_kernel)
 	{
-		// (rows walked in parts have all-one-pattern images at 4:2:0 and 4:4:4 only: launch_form)
-		if constexpr (CSUBX == CSUBY) hipLaunchKernelGGL((grain_mix_kernel<DEPTH, CSUBX, CSUBY, OUT8, true>), g, dim3(kWavesPerWG * 64), 0, stream, a, ft);
-		else return hipErrorInvalidValue;
+		// a model per frame: listed frames, every frame with a model image
+		if (!list) return false;
+		for (int i = 0; i < a.nframes; i++)
+			if (!list->model[i] || ((uintptr_t)list->model[i] & 15)) return false;
+	}
+	if (family_semiplanar(f))
+	{
+		// listed whole frames; 16-bit containers: the samples sit the same number of bits up in both halves of a dword
+		if (!list || a.y0 != 0) return false;
+		if (k.depth == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return false;
+	}
+	const bool planar_src = f == Family::p2sp || f == Family::p2sp8;
+	if (planar_src || f == Family::sp8)
+	{
+		// a destination with a geometry of its own: its rows have the source rows' containers (narrowed: as bytes), in whole dwords; a planar
+		// source: pd[1] holds ONE component's bytes of a source row and of a destination row, half a luma row's
+		const uint32_t div = k.out8 ? 2 : 1;
+		if (a.pd[1].drowbytes * div != a.pd[1].rowbytes || a.pd[0].drowbytes * div != a.pd[0].rowbytes) return false;
+		if (planar_src && a.pd[0].rowbytes != 2 * a.pd[1].rowbytes) return false;
+	}
+	if (f == Family::sp_mix && a.pd[0].rowbytes != a.pd[1].rowbytes) return false;
+	return true;
+}
+
+// grid: x = (workgroup inside the frame, frame of a group of 2^lfronts frames), y = group of frames; persist: a.persist_wgs luma workgroups
+// share the launch's luma tasks and `grid` = persist_wgs + all chroma tasks, else `grid` = workgroups per frame
+static dim3 grid_of(const KernelArgs& a, bool persist, int grid)
+{
+	return persist ? dim3((unsigned)grid) : dim3((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts);
+}
+
+// The one kernel of a key, or none: the instantiations of a code object are the keys of its depth that kernel_exists() holds, no more, no fewer
+// (tests/test_kernel_keys_cpu.py).
+template <int D, int X, int Y, bool OUT8, bool ONEY, bool ONEC, bool WIDE, bool PERSIST, Family F>
+static hipError_t launch_key(const KernelArgs& a, const FrameTable& ft, const dim3 g, hipStream_t stream)
+{
+	if constexpr (kernel_exists(KernelKey{D, X, Y, OUT8, ONEY, ONEC, WIDE, PERSIST, F}))
+	{
+		const dim3 b(kWavesPerWG * 64);
+		if constexpr (F == Family::rw) hipLaunchKernelGGL((grain_rw_kernel<D, X, Y, OUT8, ONEY, ONEC, WIDE, PERSIST>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::ml) hipLaunchKernelGGL((grain_ml_kernel<D, X, Y, ONEY, ONEC>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::mix) hipLaunchKernelGGL((grain_mix_kernel<D, X, Y, OUT8, WIDE>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::sp) hipLaunchKernelGGL((grain_sp_kernel<D, Y, ONEY, ONEC>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::spml) hipLaunchKernelGGL((grain_spml_kernel<D, Y, ONEY, ONEC>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::sp8) hipLaunchKernelGGL((grain_sp8_kernel<D, Y, ONEY, ONEC>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::p2sp) hipLaunchKernelGGL((grain_p2sp_kernel<D, Y, ONEY, ONEC>), g, b, 0, stream, a, ft);
+		else if constexpr (F == Family::p2sp8) hipLaunchKernelGGL((grain_p2sp8_kernel<D, Y, ONEY, ONEC>), g, b, 0, stream, a, ft);
+		else hipLaunchKernelGGL((grain_sp_mix_kernel<D, Y>), g, b, 0, stream, a, ft);
+		return hipGetLastError();
 	}
 	else
-		hipLaunchKernelGGL((grain_mix_kernel<DEPTH, CSUBX, CSUBY, OUT8, false>), g, dim3(kWavesPerWG * 64), 0, stream, a, ft);
-	return hipGetLastError();
+		return hipErrorInvalidValue;
 }
 
-template <int DEPTH, int CSUBX, int CSUBY, bool OUT8, bool ONEY, bool ONEC, bool WIDE, bool PERSIST>
-static hipError_t launch_t(const KernelArgs& a, const FrameTable& ft, int grid, hipStream_t stream)
+// run-time selectors -> template arguments: fn(std::bool_constant<v>{}...) for the values `v...`, one branch each
+template <bool... Bs, class Fn>
+static hipError_t lift_bools(Fn&& fn) { return fn(std::bool_constant<Bs>{}...); }
+template <bool... Bs, class Fn, class... Rest>
+static hipError_t lift_bools(Fn&& fn, bool v, Rest... rest) { return v ? lift_bools<Bs..., true>(fn, rest...) : lift_bools<Bs..., false>(fn, rest...); }
+
+template <class Fn>
+static hipError_t lift_family(Family f, Fn&& fn)
 {
-	const dim3 g = PERSIST ? dim3((unsigned)grid) : dim3((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts);
-	hipLaunchKernelGGL((grain_rw_kernel<DEPTH, CSUBX, CSUBY, OUT8, ONEY, ONEC, WIDE, PERSIST>), g, dim3(kWavesPerWG * 64), 0, stream, a, ft);
-	return hipGetLastError();
+	switch (f)
+	{
+	case Family::rw: return fn(std::integral_constant<Family, Family::rw>{});
+	case Family::ml: return fn(std::integral_constant<Family, Family::ml>{});
+	case Family::mix: return fn(std::integral_constant<Family, Family::mix>{});
+	case Family::sp: return fn(std::integral_constant<Family, Family::sp>{});
+	case Family::spml: return fn(std::integral_constant<Family, Family::spml>{});
+	case Family::sp8: return fn(std::integral_constant<Family, Family::sp8>{});
+	case Family::p2sp: return fn(std::integral_constant<Family, Family::p2sp>{});
+	case Family::p2sp8: return fn(std::integral_constant<Family, Family::p2sp8>{});
+	case Family::sp_mix: return fn(std::integral_constant<Family, Family::sp_mix>{});
+	}
+	return hipErrorInvalidValue;     // (not a Family)
 }
 
-template <int DEPTH, int CSUBX, int CSUBY, bool OUT8>
-static hipError_t launch_form(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
-{
-	if (wide)
-	{
-		// rows walked in parts: the general form for every format; at 4:2:0 and 4:4:4 also one-pattern chroma under either luma form
-		// (the default SEI model: eight luma patterns, one chroma pattern; AFGS1 and the single-pattern SEI models: one each)
-		if (persist) return hipErrorInvalidValue;
-		if constexpr (CSUBX == CSUBY)
-		{
-			if (oney && onec) return launch_t<DEPTH, CSUBX, CSUBY, OUT8, true, true, true, false>(a, ft, grid, stream);
-			if (!oney && onec) return launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, true, true, false>(a, ft, grid, stream);
-		}
-		return (oney || onec) ? hipErrorInvalidValue : launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, false, true, false>(a, ft, grid, stream);
-	}
-	if constexpr (DEPTH > 8)     // (the host asks for persistence at 10 and 12 bit only)
-	{
-		if (persist)
-		{
-			if (oney) return hipErrorInvalidValue;
-			return onec ? launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, true, false, true>(a, ft, grid, stream)
-			            : launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, false, false, true>(a, ft, grid, stream);
-		}
-	}
-	else if (persist) return hipErrorInvalidValue;
-	if (oney && onec) return launch_t<DEPTH, CSUBX, CSUBY, OUT8, true, true, false, false>(a, ft, grid, stream);
-	if (oney) return launch_t<DEPTH, CSUBX, CSUBY, OUT8, true, false, false, false>(a, ft, grid, stream);
-	if (onec) return launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, true, false, false>(a, ft, grid, stream);
-	return launch_t<DEPTH, CSUBX, CSUBY, OUT8, false, false, false, false>(a, ft, grid, stream);
-}
-
-// out8: the destination holds 8-bit samples of a 10- or 12-bit path; oney / onec: the image holds the one-pattern form for luma /
-// chroma (vfgs_layout.h); wide: rows of more than kTileBlocks blocks (launch_form: which forms exist); persist: a.persist_wgs luma workgroups
-// share the launch's luma tasks (10 and 12 bit, general-form luma, not wide), grid = persist_wgs + all chroma tasks; else grid =
-// workgroups per frame
-//
 // The product compiles this file THREE times (versatilefilmgrain_amd/build.py: -DVFGS_KERNEL_DEPTH=10, =8 and =12), side by side: one code object per
 // sample depth; the 12-bit one holds the 10-bit one's row-walk kernels (same forms, same residency) and no mix kernels.  That halves the build (110 -> 60 s) and keeps the other depth's kernels off the device; it does NOT buy the
 // start-up time round 5 hoped for: a code object's first launch costs 1.3 ms (profiles/r06_startup_probe_two_code_objects.jsonl), so the 15 ms
 // of a process's first grain launch are the allocations and first transfers around it, not the 88 kernels.  Without the macro (the assembly
 // listings) everything is one translation unit.
-template <int DEPTH, int CSUBY>
-static hipError_t launch_sp(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	if (oney && onec) hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
-	else if (oney) hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
-	else if (onec) hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
-	else hipLaunchKernelGGL((grain_sp_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
-template <int DEPTH, int CSUBY>
-static hipError_t launch_spml(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	if (oney && onec) hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
-	else if (oney) hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
-	else if (onec) hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
-	else hipLaunchKernelGGL((grain_spml_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
-template <int DEPTH, int CSUBY>
-static hipError_t launch_sp8(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	if (oney && onec) hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
-	else if (oney) hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
-	else if (onec) hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
-	else hipLaunchKernelGGL((grain_sp8_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
-template <int DEPTH, int CSUBY>
-static hipError_t launch_p2sp(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	if (oney && onec) hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
-	else if (oney) hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
-	else if (onec) hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
-	else hipLaunchKernelGGL((grain_p2sp_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
-template <int DEPTH, int CSUBY>
-static hipError_t launch_p2sp8(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	if (oney && onec) hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, true, true>), g, b, 0, stream, a, ft);
-	else if (oney) hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, true, false>), g, b, 0, stream, a, ft);
-	else if (onec) hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, false, true>), g, b, 0, stream, a, ft);
-	else hipLaunchKernelGGL((grain_p2sp8_kernel<DEPTH, CSUBY, false, false>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
-template <int DEPTH, int CSUBY>
-static hipError_t launch_sp_mix(const KernelArgs& a, const FrameTable& ft, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	hipLaunchKernelGGL((grain_sp_mix_kernel<DEPTH, CSUBY>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
-template <int DEPTH, int CSUBX, int CSUBY>
-static hipError_t launch_ml(const KernelArgs& a, const FrameTable& ft, bool oney, bool onec, int grid, hipStream_t stream)
-{
-	const dim3 g((unsigned)grid << a.lfronts, ((unsigned)a.nframes + (1u << a.lfronts) - 1) >> a.lfronts), b(kWavesPerWG * 64);
-	if (oney && onec) hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, true, true>), g, b, 0, stream, a, ft);
-	else if (oney) hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, true, false>), g, b, 0, stream, a, ft);
-	else if (onec) hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, false, true>), g, b, 0, stream, a, ft);
-	else hipLaunchKernelGGL((grain_ml_kernel<DEPTH, CSUBX, CSUBY, false, false>), g, b, 0, stream, a, ft);
-	return hipGetLastError();
-}
-
 template <int D>
-static hipError_t launch_depth(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
+static hipError_t launch_depth(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream)
 {
-	if (a.models_kernel)
-	{
-		// a model per frame: listed whole frames, planar or semi-planar (not a planar source with a semi-planar destination), rows of one parameter
-		// table, no mix, every frame with a model image (the host refuses everything else)
-		if (a.models_kernel != 1 || (a.sp_kernel != 0 && a.sp_kernel != 1) || a.mix_kernel || out8 || wide || persist || !a.listed) return hipErrorInvalidValue;
-		for (int f = 0; f < a.nframes; f++)
-			if (!ft.model[f] || ((uintptr_t)ft.model[f] & 15)) return hipErrorInvalidValue;
-		if (a.sp_kernel)
-		{
-			// (semi-planar frames: the conditions of the branch below)
-			if (csubx != 2 || a.y0 != 0) return hipErrorInvalidValue;
-			if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
-			if (csuby == 2) return launch_spml<D, 2>(a, ft, oney, onec, grid, stream);
-			if (csuby == 1) return launch_spml<D, 1>(a, ft, oney, onec, grid, stream);
-			return hipErrorInvalidValue;
-		}
-		if (csubx == 2 && csuby == 2) return launch_ml<D, 2, 2>(a, ft, oney, onec, grid, stream);
-		if (csubx == 2 && csuby == 1) return launch_ml<D, 2, 1>(a, ft, oney, onec, grid, stream);
-		if (csubx == 1 && csuby == 1) return launch_ml<D, 1, 1>(a, ft, oney, onec, grid, stream);
-		if (csubx == 1 && csuby == 2) return launch_ml<D, 1, 2>(a, ft, oney, onec, grid, stream);
-		return hipErrorInvalidValue;
-	}
-	if (a.sp_kernel)
-	{
-		// semi-planar frames: listed whole frames at 4:2:0 / 4:2:2, rows of one parameter table (the host refuses everything else)
-		if (wide || persist || csubx != 2 || !a.listed || a.y0 != 0) return hipErrorInvalidValue;
-		if (D == 8 ? a.sp_shift2 != 0 : (a.sp_shift2 >> 16) != (a.sp_shift2 & 0xffffu)) return hipErrorInvalidValue;
-		if (a.sp_kernel == 2)
-		{
-			// a planar source: no mix; pd[1] holds ONE component's bytes of a source row and of a destination row, in whole dwords -- a component's
-			// share of the UV row has the source row's containers (narrowed: as bytes), the luma row likewise
-			const uint32_t div = out8 ? 2 : 1;
-			if (a.mix_kernel || a.pd[1].drowbytes * div != a.pd[1].rowbytes || a.pd[0].drowbytes * div != a.pd[0].rowbytes || a.pd[0].rowbytes != 2 * a.pd[1].rowbytes)
-				return hipErrorInvalidValue;
-			if (out8)
-			{
-				if constexpr (D > 8)
-				{
-					if (csuby == 2) return launch_p2sp8<D, 2>(a, ft, oney, onec, grid, stream);
-					if (csuby == 1) return launch_p2sp8<D, 1>(a, ft, oney, onec, grid, stream);
-				}
-				return hipErrorInvalidValue;
-			}
-			if (csuby == 2) return launch_p2sp<D, 2>(a, ft, oney, onec, grid, stream);
-			if (csuby == 1) return launch_p2sp<D, 1>(a, ft, oney, onec, grid, stream);
-			return hipErrorInvalidValue;
-		}
-		if (a.sp_kernel != 1) return hipErrorInvalidValue;
-		if (out8)
-		{
-			// (the narrowed destination: 16-bit containers, no mix; a UV row of bytes is half the source row, whole 16-byte units)
-			if (a.mix_kernel || a.pd[1].drowbytes * 2 != a.pd[1].rowbytes || a.pd[0].drowbytes * 2 != a.pd[0].rowbytes) return hipErrorInvalidValue;
-			if constexpr (D > 8)
-			{
-				if (csuby == 2) return launch_sp8<D, 2>(a, ft, oney, onec, grid, stream);
-				if (csuby == 1) return launch_sp8<D, 1>(a, ft, oney, onec, grid, stream);
-			}
-			return hipErrorInvalidValue;
-		}
-		if (a.mix_kernel)
-		{
-			// (the mix: all-one-pattern images at 8 and 10 bit; launch_depth<12> instantiates none, the host refuses such a call before it gets here)
-			if (!oney || !onec || a.pd[0].rowbytes != a.pd[1].rowbytes) return hipErrorInvalidValue;
-			if constexpr (D != 12)
-			{
-				if (csuby == 2) return launch_sp_mix<D, 2>(a, ft, grid, stream);
-				if (csuby == 1) return launch_sp_mix<D, 1>(a, ft, grid, stream);
-			}
-			return hipErrorInvalidValue;
-		}
-		if (csuby == 2) return launch_sp<D, 2>(a, ft, oney, onec, grid, stream);
-		if (csuby == 1) return launch_sp<D, 1>(a, ft, oney, onec, grid, stream);
-		return hipErrorInvalidValue;
-	}
-	if (a.mix_kernel)
-	{
-		// (no mix kernels at 12 bit: launch_depth<12> instantiates none, the host refuses such a call before it gets here)
-		if (!oney || !onec || persist) return hipErrorInvalidValue;
-#define VFGS_CASE(X, Y)                                                                                  \
-	if (csubx == X && csuby == Y)                                                                        \
-	{                                                                                                    \
-		if constexpr (D == 10) { if (out8) return launch_mix<D, X, Y, true>(a, ft, wide, grid, stream); } \
-		if constexpr (D != 12) return launch_mix<D, X, Y, false>(a, ft, wide, grid, stream);              \
-	}
-		VFGS_CASE(2, 2) VFGS_CASE(2, 1) VFGS_CASE(1, 1) VFGS_CASE(1, 2)
-#undef VFGS_CASE
-		return hipErrorInvalidValue;
-	}
-#define VFGS_CASE(X, Y)                                                                                                     \
-	if (csubx == X && csuby == Y)                                                                                           \
-	{                                                                                                                       \
-		if constexpr (D > 8) { if (out8) return launch_form<D, X, Y, true>(a, ft, oney, onec, wide, persist, grid, stream); }   \
-		return launch_form<D, X, Y, false>(a, ft, oney, onec, wide, persist, grid, stream);                                     \
-	}
-	VFGS_CASE(2, 2) VFGS_CASE(2, 1) VFGS_CASE(1, 1) VFGS_CASE(1, 2)
-#undef VFGS_CASE
-	return hipErrorInvalidValue;
+	if (k.depth != D || (k.csubx != 1 && k.csubx != 2) || (k.csuby != 1 && k.csuby != 2) || !launch_args_ok(a, list, k)) return hipErrorInvalidValue;
+	static const FrameTable no_list{};
+	const FrameTable& ft = list ? *list : no_list;
+	const dim3 g = grid_of(a, k.persist, grid);
+	return lift_family(k.family, [&](auto F) {
+		return lift_bools([&](auto X2, auto Y2, auto OUT8, auto ONEY, auto ONEC, auto WIDE, auto PERSIST) {
+			return launch_key<D, X2() ? 2 : 1, Y2() ? 2 : 1, OUT8(), ONEY(), ONEC(), WIDE(), PERSIST(), decltype(F)::value>(a, ft, g, stream);
+		}, k.csubx == 2, k.csuby == 2, k.out8, k.oney, k.onec, k.wide, k.persist);
+	});
 }
 
 #if !defined(VFGS_KERNEL_DEPTH) || VFGS_KERNEL_DEPTH == 8
-hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
-{
-	return launch_depth<8>(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
-}
+hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream) { return launch_depth<8>(a, list, k, grid, stream); }
 #else
-hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream);
+hipError_t launch_grain_d8(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream);
 #endif
 
 #if !defined(VFGS_KERNEL_DEPTH) || VFGS_KERNEL_DEPTH == 12
-hipError_t launch_grain_d12(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
-{
-	return launch_depth<12>(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
-}
+hipError_t launch_grain_d12(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream) { return launch_depth<12>(a, list, k, grid, stream); }
 #else
-hipError_t launch_grain_d12(const KernelArgs& a, const FrameTable& ft, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream);
+hipError_t launch_grain_d12(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream);
 #endif
 
 #if !defined(VFGS_KERNEL_DEPTH) || VFGS_KERNEL_DEPTH == 10
-hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist, int grid, hipStream_t stream)
+hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream)
 {
-	if ((out8 && depth != 10 && depth != 12) || wide != (a.nblk > kTileBlocks)) return hipErrorInvalidValue;
-	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return hipErrorInvalidValue;
-	if ((a.listed != 0) != (list != nullptr) || (list && a.nframes > kListFrames)) return hipErrorInvalidValue;
-	static const FrameTable no_list{};
-	const FrameTable& ft = list ? *list : no_list;
-	if (depth == 10) return launch_depth<10>(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
-	if (depth == 8) return launch_grain_d8(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
-	if (depth == 12) return launch_grain_d12(a, ft, csubx, csuby, out8, oney, onec, wide, persist, grid, stream);
-	return hipErrorInvalidValue;
+	if (k.depth == 10) return launch_depth<10>(a, list, k, grid, stream);
+	if (k.depth == 8) return launch_grain_d8(a, list, k, grid, stream);
+	return launch_grain_d12(a, list, k, grid, stream);
 }
 
-// the name of the instantiation launch_grain() dispatches for these arguments, as the profiler prints it (vfgs_hip_last_launch_info)
-void describe_launch(char* out, size_t n, int depth, int csubx, int csuby, bool out8, bool oney, bool onec, bool wide, bool persist)
-{
-	auto b = [](bool v) { return v ? "true" : "false"; };
-	snprintf(out, n, "grain_rw_kernel<%d,%d,%d,%s,%s,%s,%s,%s>", depth, csubx, csuby, b(out8), b(oney), b(onec), b(wide), b(persist));
-}
+// the name of the kernel launch_grain() dispatches for a key, as the launch record states it (vfgs_hip_last_launch_info)
+void name_launch(const KernelKey& k, char* out, size_t n) { kernel_name(k, out, n); }
 
 ImageLayout layout_of(int csubx, int csuby, bool oney, bool onec, bool depth8) { return image_layout(csubx, csuby, oney, onec, depth8); }
 #endif

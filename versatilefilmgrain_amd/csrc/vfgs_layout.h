@@ -1,7 +1,9 @@
 // Shared between the host state machine (vfgs_host.cpp) and the gfx950 kernels
 // (vfgs_kernel.hip): the LDS image of the pattern banks + LUTs and the launch record.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace vfgs {
 
@@ -315,5 +317,105 @@ struct KernelArgs {
 	uint32_t sp_shift2;       // ... 16-bit containers: the samples sit this many bits up (P010: 6, P012: 4), in both halves of the dword (a packed 16-bit shift each way)
 };
 static_assert(sizeof(KernelArgs) == 304, "the frame table follows KernelArgs in the kernel arguments: a new size moves what every kernel loads from it");
+
+// WHICH kernel serves a launch: the kernel family and its template arguments.  The host forms one key per call (vfgs_host.cpp Launch::key), the
+// launcher instantiates and dispatches from kernel_exists() (vfgs_kernel.hip launch_key), the launch record names the kernel and its LDS with
+// kernel_name() / kernel_lds_bytes(), and tests/test_kernel_keys_cpu.py holds all three against the kernels in the built code objects.
+enum class Family {
+	rw,        // grain_rw_kernel    <depth, csubx, csuby, out8, oney, onec, wide, persist>: planar frames
+	ml,        // grain_ml_kernel    <depth, csubx, csuby, oney, onec>: ... with a model per frame
+	mix,       // grain_mix_kernel   <depth, csubx, csuby, out8, wide>: ... under the luma / chroma mix
+	sp,        // grain_sp_kernel    <depth, csuby, oney, onec>: semi-planar frames
+	spml,      // grain_spml_kernel  <depth, csuby, oney, onec>: ... with a model per frame
+	sp8,       // grain_sp8_kernel   <depth, csuby, oney, onec>: ... with the narrowed 8-bit destination
+	p2sp,      // grain_p2sp_kernel  <depth, csuby, oney, onec>: a planar source, a semi-planar destination
+	p2sp8,     // grain_p2sp8_kernel <depth, csuby, oney, onec>: ... narrowed
+	sp_mix,    // grain_sp_mix_kernel<depth, csuby>: semi-planar frames under the mix
+};
+
+struct KernelKey {
+	int depth, csubx, csuby;
+	// out8: the destination holds 8-bit samples of a 10- or 12-bit path; oney / onec: the image holds the one-pattern form for luma / chroma;
+	// wide: rows of more than kTileBlocks blocks; persist: KernelArgs::persist_wgs luma workgroups share the launch's luma tasks
+	bool out8, oney, onec, wide, persist;
+	Family family;
+};
+
+constexpr bool family_semiplanar(const Family f) { return f != Family::rw && f != Family::ml && f != Family::mix; }     // (the destination is; p2sp: not the source)
+
+// The family as KernelArgs states it (no kernel reads these three fields; the launcher refuses a key that disagrees with them).  out8 is the
+// key's: it tells sp8 from sp and p2sp8 from p2sp.
+struct FamilyFields { int models_kernel, mix_kernel, sp_kernel; };
+constexpr FamilyFields family_fields(const Family f)
+{
+	return FamilyFields{f == Family::ml || f == Family::spml, f == Family::mix || f == Family::sp_mix,
+	                    !family_semiplanar(f) ? 0 : ((f == Family::p2sp || f == Family::p2sp8) ? 2 : 1)};
+}
+
+// THE TABLE OF INSTANTIATIONS.  A family pins every parameter it does not take, so one kernel has exactly one key.
+constexpr bool kernel_exists(const KernelKey& k)
+{
+	if ((k.depth != 8 && k.depth != 10 && k.depth != 12) || (k.csubx != 1 && k.csubx != 2) || (k.csuby != 1 && k.csuby != 2)) return false;
+	const bool all_one = k.oney && k.onec, square = k.csubx == k.csuby;      // (square: 4:2:0 and 4:4:4)
+	// semi-planar frames: 4:2:0 / 4:2:2, rows of one parameter table, no persistent luma workgroups
+	if (family_semiplanar(k.family) && (k.csubx != 2 || k.wide || k.persist)) return false;
+	switch (k.family)
+	{
+	case Family::rw:
+		if (k.out8 && k.depth == 8) return false;
+		// rows walked in parts: the general form for every format; at 4:2:0 and 4:4:4 also one-pattern chroma under either luma form
+		// (the default SEI model: eight luma patterns, one chroma pattern; AFGS1 and the single-pattern SEI models: one each)
+		if (k.wide) return !k.persist && (k.oney ? k.onec && square : !k.onec || square);
+		// persistence: 10 and 12 bit, general-form luma
+		return !k.persist || (k.depth > 8 && !k.oney);
+	case Family::ml:
+		return !k.out8 && !k.wide && !k.persist;
+	case Family::mix:       // all-one-pattern images at 8 and 10 bit; the 8-bit destination at 10 bit; rows walked in parts at 4:2:0 and 4:4:4
+		return all_one && !k.persist && k.depth != 12 && (!k.out8 || k.depth == 10) && (!k.wide || square);
+	case Family::sp: case Family::spml: case Family::p2sp:
+		return !k.out8;
+	case Family::sp8: case Family::p2sp8:
+		return k.out8 && k.depth > 8;
+	case Family::sp_mix:
+		return !k.out8 && all_one && k.depth != 12;
+	}
+	return false;
+}
+
+// what that kernel's __shared__ array is sized to
+constexpr int kernel_lds_bytes(const KernelKey& k)
+{
+	const ImageLayout L = image_layout(k.csubx, k.csuby, k.oney, k.onec, k.depth == 8);
+	switch (k.family)
+	{
+	case Family::rw: case Family::ml: return lds_allocation(k.depth > 8, k.oney, k.onec, k.wide, L.lds_bytes + kParamBytes);
+	case Family::mix: return mix_lds_allocation(L.lds_bytes + kParamBytes);
+	case Family::sp_mix: return sp_mix_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, true));
+	case Family::sp: case Family::spml: case Family::sp8: case Family::p2sp: case Family::p2sp8:
+		return sp_lds_allocation(sp_lds_need(L.y_bytes, L.c_bytes, L.lut_bytes, k.onec));
+	}
+	return 0;
+}
+
+// the kernel's name as the profiler prints it (vfgs_hip_last_launch_info): the template arguments its family takes, in the order of the table above
+// (not constexpr: it formats with snprintf)
+inline int kernel_name(const KernelKey& k, char* out, const size_t n)
+{
+	auto b = [](bool v) { return v ? "true" : "false"; };
+	auto sp = [&](const char* name) { return snprintf(out, n, "%s<%d,%d,%s,%s>", name, k.depth, k.csuby, b(k.oney), b(k.onec)); };
+	switch (k.family)
+	{
+	case Family::rw: return snprintf(out, n, "grain_rw_kernel<%d,%d,%d,%s,%s,%s,%s,%s>", k.depth, k.csubx, k.csuby, b(k.out8), b(k.oney), b(k.onec), b(k.wide), b(k.persist));
+	case Family::ml: return snprintf(out, n, "grain_ml_kernel<%d,%d,%d,%s,%s>", k.depth, k.csubx, k.csuby, b(k.oney), b(k.onec));
+	case Family::mix: return snprintf(out, n, "grain_mix_kernel<%d,%d,%d,%s,%s>", k.depth, k.csubx, k.csuby, b(k.out8), b(k.wide));
+	case Family::sp_mix: return snprintf(out, n, "grain_sp_mix_kernel<%d,%d>", k.depth, k.csuby);
+	case Family::sp: return sp("grain_sp_kernel");
+	case Family::spml: return sp("grain_spml_kernel");
+	case Family::sp8: return sp("grain_sp8_kernel");
+	case Family::p2sp: return sp("grain_p2sp_kernel");
+	case Family::p2sp8: return sp("grain_p2sp8_kernel");
+	}
+	return snprintf(out, n, "?");
+}
 
 }  // namespace vfgs
