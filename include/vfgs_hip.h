@@ -26,6 +26,7 @@
 #ifndef VFGS_HIP_H
 #define VFGS_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -377,6 +378,19 @@ typedef struct vfgs_hip_model vfgs_hip_model;                 /* opaque */
 int  vfgs_hip_model_capture(vfgs_hip_model** out, void* stream);
 void vfgs_hip_model_release(vfgs_hip_model* m);
 int  vfgs_hip_model_info(const vfgs_hip_model* m, int out[8]);
+
+/* Read back what a model holds on the device: the 32-byte record (clip bounds, the packed form's shift) followed by the table image, *bytes
+ * (may be NULL) = their size = out[7] of vfgs_hip_model_info.  Synchronises (it waits for the work that made the model, on whatever stream);
+ * for tests and debugging, like vfgs_hip_get_pattern.  41: a null or released handle; 6: `cap` is smaller than the size (or `out` is NULL),
+ * with *bytes set to the size needed.  Serves captured models and models built from parameter sets (vfgs_hip_models_from_afgs1,
+ * vfgs_hip_fw.h) alike. */
+int  vfgs_hip_model_image(const vfgs_hip_model* m, void* out, size_t cap, size_t* bytes);
+
+/* Bookkeeping of vfgs_hip_models_from_afgs1 (vfgs_hip_fw.h), in the style of vfgs_hip_get_seeded_stream_stats: out[8] = { calls that built,
+ * models built, kernel launches, copies queued, device allocations (one slab each, with its pinned job table), device frees, models per
+ * launch (the constant), 0 }.  A refused call changes none of them; in the steady state of build / grain / release the allocations and frees
+ * stand still. */
+void vfgs_hip_get_model_build_stats(uint64_t out[8]);
 
 /* The list call with A MODEL PER PICTURE.  src / dst / seeds / geometry exactly as in vfgs_hip_add_grain_frame_list[_seeded]_copy_dev
  * (src == dst, or dst[f]'s plane == src[f]'s plane: in place; seeds NULL: one seed sequence, frame f + 1 continues frame f's registers;

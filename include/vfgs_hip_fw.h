@@ -98,6 +98,33 @@ void vfgs_hip_afgs1_chroma_mix(int enable);
  * vfgs_hip_add_grain_frame_list_seeded_dev (vfgs_hip.h) -- this is the seed of each.  Host only, no GPU needed. */
 unsigned int vfgs_hip_afgs1_seed(const fgs_afgs1* cfg);
 
+/* MODELS STRAIGHT FROM PARAMETER SETS, a batch per launch.  A player that receives an AFGS1 parameter set with every picture gets its
+ * models (vfgs_hip.h "models as objects") without programming anything: at the programmed depth and chroma format (vfgs_set_depth,
+ * vfgs_set_chroma_subsampling) out[i] is a live model that no call taking models -- the two list calls with a model per picture,
+ * vfgs_hip_model_info, vfgs_hip_model_release -- can tell apart from the result of
+ *     vfgs_hip_afgs1_chroma_mix(0); vfgs_init_afgs1(&cfgs[i]); vfgs_hip_model_capture(&out[i], stream);
+ * including the form of its image (at 8 bit a component whose scaling function does not fit the packed 16-bit form falls back to the
+ * general form; the slots no LUT selects are zero there) and the reference firmware's quirks as vfgs_init_afgs1 restates them.
+ * The PROGRAMMED STATE IS UNTOUCHED: host mirror, device pattern banks, pending pattern requests, table images, depth and format, the four
+ * seed registers, the chroma mix and its switch are what they were.  The picture's seed stays the caller's business --
+ * vfgs_hip_afgs1_seed(&cfgs[i]) goes into the list call's `seeds` -- and cb_mult and the other mix fields are ignored: a model carries
+ * no mix, as with capture.
+ * One kernel serves up to 32 models (one workgroup each: the luma and the Cb recursion side by side, then the whole record + image
+ * written from LDS), so a call queues ONE copy (the job table) and ONE launch per 32 models; the models of such a chunk share one device
+ * allocation that returns to a small pool with the last release: no allocation and no free in the steady state of build / grain / release
+ * (vfgs_hip_get_model_build_stats, vfgs_hip.h).  Asynchronous on `stream`; a first use on another stream waits by event; inside an
+ * overlap region pass the region's stream.
+ * REFUSALS replace vfgs_init_afgs1's aborts.  A refused call builds nothing, sets out[0..n) to NULL, queues nothing and changes no
+ * statistic; the message names the index and the cause:
+ *   41  out == NULL, or cfgs == NULL (n > 0)
+ *   42  ar_coeff_lag outside 1..3; num_y_points > 14, num_cb_points / num_cr_points > 10; scaling points not strictly increasing in a
+ *       function that is used (Cb's and Cr's are not with chroma_scaling_from_luma); ar_coeff_shift outside 1..15; grain_scale_shift > 6
+ *    9  the scale shift that vfgs_set_scale_shift(grain_scaling - 6) would store is out of range at the programmed depth (vfgs_hw.c:170),
+ *       exactly as vfgs_hip_model_capture refuses it: grain_scaling outside 8..13
+ * n == 0 is no call at all and returns 0. */
+struct vfgs_hip_model;
+int vfgs_hip_models_from_afgs1(const fgs_afgs1* cfgs, unsigned n, struct vfgs_hip_model** out, void* stream);
+
 /* One grain pattern to be generated on the device into pattern slot `index`. */
 typedef struct vfgs_hip_pattern_job {
 	int32_t kind;       /* 0: frequency filtered (vfgs_fw.c:362-408), 1: auto-regressive (vfgs_fw.c:410-502) */

@@ -17,6 +17,7 @@
 
 #include "../../include/vfgs_hip.h"
 #include "../../include/vfgs_hip_fw.h"
+#include "vfgs_fw_afgs1.h"
 
 namespace {
 
@@ -174,32 +175,13 @@ void sei_luts(const fgs_sei* cfg, const PatternList& pl, int c, unsigned char sl
 
 // ---- AFGS1 -----------------------------------------------------------------------------
 
-// AFGS1 scaling function -> scale LUT: zero outside the points, between two points the rounded interpolation of
-// vfgs_fw.c:649-661 (integer division that truncates towards zero, also for falling segments).  Segments are half-open
-// [x[s], x[s+1]): the reference writes every segment including its end point and the next segment then rewrites that
-// entry with its own start value -- the same bytes; only the last segment keeps its end point.
+// the scaling function and the tap order: vfgs_fw_afgs1.h, shared with vfgs_hip_models_from_afgs1 (which refuses where this aborts)
+using vfgs::afgs1_taps;
+
 void scaling_lut(unsigned char lut[256], const unsigned char* x, const unsigned char* y, int npoints)
 {
-	memset(lut, 0, 256);
-	for (int s = 0; s + 1 < npoints; s++)
-	{
-		const int x0 = x[s], span = x[s + 1] - x0, rise = (int)y[s + 1] - (int)y[s];
-		if (span <= 0)
-			fw_die("AFGS1 scaling points must be in increasing order (vfgs_fw.c:656)");
-		const int stop = x0 + span + (s + 2 == npoints ? 1 : 0);
-		for (int t = x0; t < stop; t++)
-			lut[t] = (unsigned char)(y[s] + (rise * (t - x0) + span / 2) / span);
-	}
-}
-
-// AV1 order of the causal neighbourhood -> 4x7 tap matrix (vfgs_fw.c:461-464)
-void afgs1_taps(const int16_t* ar, int lag, int16_t coef[28])
-{
-	memset(coef, 0, 28 * sizeof(int16_t));
-	int k = 0;
-	for (int j = -lag; j <= 0; j++)
-		for (int i = -lag; i <= lag && (i < 0 || j < 0); i++)
-			coef[(3 + j) * 7 + 3 + i] = ar[k++];
+	if (!vfgs::afgs1_scaling_lut(lut, x, y, npoints))
+		fw_die("AFGS1 scaling points must be in increasing order (vfgs_fw.c:656)");
 }
 
 }  // namespace

@@ -24,6 +24,7 @@
 
 #include "vfgs_fw_layout.h"
 #include "vfgs_layout.h"
+#include "vfgs_model_build.h"
 
 namespace vfgs {
 namespace {
@@ -164,7 +165,10 @@ __device__ inline int mad24(int a, int b, int c)
 	return d;
 }
 
-template <int L>
+// Caller: one instantiation per kernel that runs the recursion (0: fw_ar_kernel, 1: fw_models_kernel).  The optimiser propagates what a
+// function's ONLY caller passes into it before it inlines; with one instantiation for both, fw_ar_kernel would come out with other -- equivalent
+// -- instructions than the ones that were measured (tools/dev/compare_code_objects.py).
+template <int L, int Caller = 0>
 __device__ __forceinline__ void ar_rows(int8_t* buf, const short* coef, int width, int height, int scale, int lane)
 {
 	constexpr int K = L + 1, WN = 2 * L + 1;
@@ -325,6 +329,128 @@ __global__ __launch_bounds__(256) void fw_commit_chroma(FwLaunch L)
 }
 
 // ---------------------------------------------------------------------------------------
+// Whole models from AFGS1 parameter sets (vfgs_hip_models_from_afgs1, vfgs_model_build.h): one workgroup per model, a chunk of models
+// per launch.  What the capture path does in three pattern jobs, a bank copy, a host-built image, an upload and fw_patch_tables
+// happens here between LDS and the model's own buffer: the luma and the Cb recursion run side by side in two wavefronts (the
+// work is one dependent chain per pattern; Cr's pattern is never selected, vfgs_fw.c:700-703 with vfgs_hw.c:212, and is not made),
+// and then all four wavefronts write record, zero fill, scale tables and banks -- image_layout's bytes exactly as build_tables and
+// fw_patch_tables leave them for a state that vfgs_init_afgs1 programmed.  Nothing visits a pattern bank in global memory.
+//
+// ar_rows<L> is shared with fw_ar_kernel as it stands, in an instantiation of this kernel's own (see there).
+__device__ __forceinline__ void ar_pattern(int8_t* buf, const short* coef, int width, int height, int scale, int lag, int lane)
+{
+	if (lag == 1) ar_rows<1, 1>(buf, coef, width, height, scale, lane);
+	else if (lag == 2) ar_rows<2, 1>(buf, coef, width, height, scale, lane);
+	else ar_rows<3, 1>(buf, coef, width, height, scale, lane);
+}
+
+// one bank of the image from a pattern v(row, column): the general form holds it as slot 0 of the slot-interleaved bank (the slots no
+// LUT selects stay zero), the one-pattern form as bytes -- int16 values in the packed 16-bit form -- followed by the negated copy
+template <typename F>
+__device__ __forceinline__ void write_bank(uint8_t* bank, int rs, int neg, int rows, int cols, bool one, bool pk16, int tid, F v)
+{
+	if (!one)
+		for (int o = tid; o < rows * cols; o += 256)
+		{
+			const int r = o / cols, x = o % cols;
+			*(uint2*)(bank + r * rs + x * kSlots) = make_uint2((uint32_t)(uint8_t)v(r, x), 0u);
+		}
+	else if (pk16)
+		for (int o = tid; o < rows * cols / 2; o += 256)
+		{
+			const int r = o / (cols / 2), x = 2 * (o % (cols / 2));
+			const int a = v(r, x), b = v(r, x + 1);
+			*(uint32_t*)(bank + r * rs + 2 * x) = (uint32_t)(uint16_t)a | ((uint32_t)(uint16_t)b << 16);
+			*(uint32_t*)(bank + neg + r * rs + 2 * x) = (uint32_t)(uint16_t)-a | ((uint32_t)(uint16_t)-b << 16);
+		}
+	else
+		for (int o = tid; o < rows * cols / 4; o += 256)
+		{
+			const int r = o / (cols / 4), x = 4 * (o % (cols / 4));
+			uint32_t p = 0, n = 0;
+			for (int q = 0; q < 4; q++)
+			{
+				const int a = v(r, x + q);
+				p |= (uint32_t)(uint8_t)a << (8 * q);
+				n |= (uint32_t)(uint8_t)-a << (8 * q);
+			}
+			*(uint32_t*)(bank + r * rs + x) = p;
+			*(uint32_t*)(bank + neg + r * rs + x) = n;
+		}
+}
+
+__global__ __launch_bounds__(256) void fw_models_kernel(const FwConstants* __restrict__ k, const FwModelJob* __restrict__ jobs, int csubx, int csuby, int depth8)
+{
+	const FwModelJob& jb = jobs[blockIdx.x];
+	// guard zones as in fw_ar_kernel: reads of positions a row has not reached / has left lie at most 3 rows + 3 columns in front of
+	// the buffer; behind it, the luma walk reaches 128 cells, and the lanes 38..63 of the chroma walk (rows the buffer does not have:
+	// nothing of theirs is stored) read up to row 63's cells -- kFwArenaChroma covers 64 rows
+	constexpr int kArGuardLo = 256;
+	__shared__ __attribute__((aligned(16))) int8_t arena_y[kFwArenaLuma];
+	__shared__ __attribute__((aligned(16))) int8_t arena_c[kFwArenaChroma];
+	__shared__ __attribute__((aligned(16))) int8_t G[2048];
+	__shared__ uint32_t W[2][kFwStreamWords];
+	static_assert(sizeof arena_y + sizeof arena_c + sizeof G + sizeof W == kFwModelsLdsBytes, "vfgs_model_build.h states the group segment");
+	int8_t* const by = arena_y + kArGuardLo;
+	int8_t* const bc = arena_c + kArGuardLo;
+	const int tid = threadIdx.x;
+	const int shift = jb.shift;
+
+	for (int i = tid; i < 512; i += 256) ((uint32_t*)G)[i] = ((const uint32_t*)k->gauss)[i];
+	for (int i = tid; i < 2 * kFwStreamWords; i += 256) (&W[0][0])[i] = (&k->stream[0][0])[i];    // seed indices 0 (luma) and 1 (Cb), vfgs_fw.c:689, :693
+	__syncthreads();
+	// the noise term of every sample (vfgs_fw.c:492-493): one generator step per sample in raster order
+	for (int n = tid; n < 82 * 73; n += 256)
+		by[n] = (int8_t)(((int)G[noise_index(W[0], n)] + (1 << (shift - 1))) >> shift);
+	for (int n = tid; n < 44 * 38; n += 256)
+		bc[n] = (int8_t)(((int)G[noise_index(W[1], n)] + (1 << (shift - 1))) >> shift);
+	__syncthreads();
+
+	// two recursions, two wavefronts (the index is made wave-uniform: the taps are scalar operands of ar_rows' multiplies)
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	if (wave == 0) ar_pattern(by, jb.coef[0], 82, 73, jb.scale, jb.lag, tid);
+	else if (wave == 1) ar_pattern(bc, jb.coef[1], 44, 38, jb.scale, jb.lag, tid & 63);
+	__syncthreads();
+
+	// ---- the model: record, zero fill, then every byte that is not zero
+	const bool pk16 = depth8 && kPk16, one_y = jb.one_y != 0, one_c = jb.one_c != 0;
+	const ImageLayout L = image_layout(csubx, csuby, one_y, one_c, depth8 != 0);
+	uint8_t* const img = jb.dst + kModelRecordBytes;
+	if (tid < kModelRecordBytes / 4) ((uint32_t*)jb.dst)[tid] = ((const uint32_t*)&jb.rec)[tid];
+	for (int o = tid; o < L.bytes / 16; o += 256) ((uint4*)img)[o] = make_uint4(0u, 0u, 0u, 0u);
+	__threadfence();     // (the zeros have arrived before another wavefront stores to the same bytes)
+	__syncthreads();
+
+	// scale tables: build_tables' entries -- every pattern LUT of an AFGS1 model selects slot 0 (Cr's value of 1 too: the slot is bits 7:4)
+	for (int c = 0; c < 3; c++)
+	{
+		const bool one = c ? one_c : one_y;
+		uint32_t* lut = (uint32_t*)(c == 0 ? img + L.y_off : img + L.c_off[c - 1] + L.c_lut[c - 1]);
+		if (pk16 && one)
+		{
+			if (tid < 64) lut[tid] = ((const uint32_t*)jb.slut[c])[tid];     // the scale bytes themselves
+			continue;
+		}
+		const int sc = (int)jb.slut[c][tid] << (16 - jb.scale_shift);
+		lut[tid] = (uint32_t)sc & 0xffffffu;
+		if (!one) lut[256 + tid] = (uint32_t)(-sc) & 0xffffffu;
+	}
+
+	// the crops (vfgs_fw.c:498-501): 64x64 at (9, 9) of the luma buffer, 32x32 at (6, 6) of the chroma buffer
+	auto luma = [&](int r, int x) { return (int)by[82 * (9 + r) + 9 + x]; };
+	auto raw = [&](int i) { return (int)bc[44 * (6 + (i >> 5)) + 6 + (i & 31)]; };
+	// chroma slot 0 as the bank copy leaves it (vfgs_hw.c:320-325): read with pitch 64/csuby from a 64x64 scratch buffer whose first 1024
+	// bytes are the chroma pattern and whose tail is this set's luma pattern (fw_commit_chroma); at 4:2:0 pitch = length = 32
+	auto chroma = [&](int r, int x) {
+		const int i = (64 / csuby) * r + x;
+		return i < 1024 ? raw(i) : luma(i >> 6, i & 63);
+	};
+	write_bank(img + L.y_off + L.y_bank, L.y_rs, L.y_neg, 64, 64, one_y, pk16, tid, luma);
+	for (int c = 0; c < 2; c++)     // Cb and Cr: the same pattern in both sub-images
+		write_bank(img + L.c_off[c] + L.c_bank, L.c_rs, L.c_neg, L.ch, L.cw, one_c, pk16, tid, chroma);
+}
+
+// ---------------------------------------------------------------------------------------
 // Copy device-generated slots into a device image (image_layout of vfgs_layout.h) that the host
 // has just uploaded with the host-set slots and the LUTs.  one_*: that plane type is stored in the
 // one-pattern form, holding slot slot_y / slot_cb / slot_cr only (8 = the all-zero pattern: nothing to copy).
@@ -401,6 +527,13 @@ __global__ __launch_bounds__(256) void fw_patch_tables(const PatchArgs p)
 }
 
 }  // namespace
+
+hipError_t launch_fw_models(const FwConstants* k, const FwModelJob* jobs, int n, int csubx, int csuby, int depth8, hipStream_t stream)
+{
+	if (n <= 0 || n > kFwModelChunk) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(fw_models_kernel, dim3(n), dim3(256), 0, stream, k, jobs, csubx, csuby, depth8);
+	return hipGetLastError();
+}
 
 hipError_t launch_fw_generate(const FwLaunch& L, hipStream_t stream)
 {

@@ -26,6 +26,7 @@
 #include "../../include/vfgs_hip_fw.h"
 #include "vfgs_fw_layout.h"
 #include "vfgs_layout.h"
+#include "vfgs_model_build.h"
 
 namespace vfgs {
 hipError_t launch_grain(const KernelArgs& a, const FrameTable* list, const KernelKey& k, int grid, hipStream_t stream);
@@ -1293,6 +1294,15 @@ int check_luts(State& s)
 	return 0;
 }
 
+// image_form's test of one scale LUT for the packed 16-bit form (explained there); also asked for the models built from parameter sets (build_models)
+bool lut_fits16(int bs, int scale_shift, const uint8_t (&lut)[256])
+{
+	if (bs != 0 || !vfgs::kPk16) return true;
+	int mx = 0;
+	for (int i = 0; i < 256; i++) mx = std::max(mx, (int)lut[i]);
+	return mx * 127 + (1 << (scale_shift - 1)) <= 32767;
+}
+
 // Which form of the table image (vfgs_layout.h) the current state gets.  wide: the picture is wider than 8192 samples (rows walked
 // in parts); those kernels exist for the combinations that matter there -- everything general, one-pattern chroma under general
 // or one-pattern luma, at 4:2:0 and 4:4:4 (vfgs_layout.h kernel_exists) -- and every other case gets the general form even where
@@ -1316,12 +1326,7 @@ void image_form(const State& s, bool wide, bool* one_y, bool* one_c)
 	// 8 bit: the one-pattern form multiplies pattern and scale in 16 bits, two samples per instruction (vfgs_layout.h "packed 16-bit
 	// form"; vfgs_hw.c:263): |P| <= 127 (no -128, above), so the form is exact while max(scale) * 127 + 2^(shift-1) fits an int16
 	// -- scale <= 249 at the usual shift of 11; a LUT beyond that keeps the general form
-	auto fits16 = [&](int c) {
-		if (s.bs != 0 || !vfgs::kPk16) return true;
-		int mx = 0;
-		for (int i = 0; i < 256; i++) mx = std::max(mx, (int)s.slut[c][i]);
-		return mx * 127 + (1 << (s.scale_shift - 1)) <= 32767;
-	};
+	auto fits16 = [&](int c) { return lut_fits16(s.bs, s.scale_shift, s.slut[c]); };
 	*one_y = !want_general && slot[0] >= 0 && negatable(0, slot[0]) && fits16(0);
 	*one_c = !want_general && slot[1] >= 0 && slot[2] >= 0 && negatable(1, slot[1]) && negatable(1, slot[2]) && fits16(1) && fits16(2);
 	if (wide && !(s.csubx == s.csuby && *one_c)) *one_y = *one_c = false;
@@ -1440,6 +1445,19 @@ void load_seed(State& s, uint32_t seed)
 // its SlotGuard makes a first use on another stream wait for that upload (an event, no host wait) and remembers the streams that read it.
 // A released model's buffers go to a short queue with the events of those streams: they are handed to a later capture, or freed, only
 // after every launch queued before the release is done.
+//
+// Models built from parameter sets (vfgs_hip_models_from_afgs1 -> build_models) are written by ONE kernel per chunk of kFwModelChunk and
+// share one device allocation, the chunk's SLAB: the job table the kernel reads, then every model's record + image at a 16-byte aligned
+// offset.  The slab has the one SlotGuard of its models (one upload event per chunk, the streams that read any of them) and counts the
+// models not yet released; with the last release it is left like a captured model's buffers and waits in a short queue for the next
+// build, which takes it once its readers are done -- no allocation and no hipFree (which synchronises the device) in the steady state.
+struct ModelSlab {
+	uint8_t* dev = nullptr;               // [kFwModelChunk] FwModelJob, then the models
+	vfgs::FwModelJob* stage = nullptr;    // pinned source of the job table's copy
+	size_t cap = 0;
+	unsigned live = 0;                    // models of the slab that are not released yet
+	SlotGuard guard;
+};
 }  // namespace
 
 struct vfgs_hip_model {
@@ -1451,6 +1469,7 @@ struct vfgs_hip_model {
 	vfgs::ModelRecord rec{};
 	size_t cap = 0, bytes = 0;
 	SlotGuard guard;
+	ModelSlab* slab = nullptr;    // a built model: dev points into this slab, host is null, and the guard is the slab's
 };
 
 namespace {
@@ -1463,14 +1482,34 @@ struct ModelRun {                 // what run_device needs to know about the mod
 std::vector<vfgs_hip_model*> g_models;        // live models (a handle that is not in here is refused, or ignored by release)
 std::vector<vfgs_hip_model*> g_models_left;   // released, oldest first: buffers that queued launches may still read
 constexpr size_t kModelsLeftMax = 8;
+std::vector<ModelSlab*> g_slabs_idle;         // slabs whose models are all released, oldest first: queued launches may still read them
+constexpr size_t kSlabsIdleMax = 4;
+// vfgs_hip_get_model_build_stats: calls that built, models built, kernel launches, copies queued, slab allocations, slab frees
+uint64_t g_build_stats[6] = {};
 
 bool model_live(const vfgs_hip_model* m)
 {
 	return m && std::find(g_models.begin(), g_models.end(), m) != g_models.end();
 }
 
+SlotGuard& model_guard(vfgs_hip_model* m) { return m->slab ? m->slab->guard : m->guard; }
+
+void slab_destroy(ModelSlab* sl)              // (its readers are done)
+{
+	if (sl->dev) { (void)hipFree(sl->dev); g_build_stats[5]++; }
+	if (sl->stage) (void)hipHostFree(sl->stage);
+	sl->guard.destroy();
+	delete sl;
+}
+
 void model_destroy(vfgs_hip_model* m)         // (its readers are done)
 {
+	if (m->slab)
+	{
+		if (--m->slab->live == 0) slab_destroy(m->slab);
+		delete m;
+		return;
+	}
 	if (m->dev) (void)hipFree(m->dev);
 	if (m->host) (void)hipHostFree(m->host);
 	m->guard.destroy();
@@ -1482,8 +1521,10 @@ void release_models()
 {
 	for (vfgs_hip_model* m : g_models) model_destroy(m);
 	for (vfgs_hip_model* m : g_models_left) model_destroy(m);
+	for (ModelSlab* sl : g_slabs_idle) slab_destroy(sl);
 	g_models.clear();
 	g_models_left.clear();
+	g_slabs_idle.clear();
 }
 
 // ------------------------------------------------------------------------------------
@@ -2683,6 +2724,104 @@ hipStream_t pick_stream(void* stream)
 namespace vfgs {
 // for the other host files of the library (vfgs_cfg_host.cpp): record an error like fail()
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
+// Models from parameter sets (vfgs_model_build.h): the side of vfgs_hip_models_from_afgs1 that knows the programmed depth and format, the
+// slabs and the handles.  The programmed state is only READ here: no pending pattern request is flushed, nothing is generated into the
+// pattern banks, and the table ring, tables_dirty, the seeds and the mix are not looked at.
+int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model** out, void* stream_, FwModelsLauncher launch)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (int e = ensure_init(-1)) return e;
+	State& s = g_states[0];
+	const bool d8 = s.bs == 0;
+	for (unsigned i = 0; i < n; i++)
+	{
+		// FwModelJob::scale_shift arrives as the argument of vfgs_set_scale_shift and leaves as what that setter stores (vfgs_hw.c:349)
+		const int stored = jobs[i].scale_shift + 6 - s.bs;
+		if (stored + s.bs < 8 || stored + s.bs > 13)   // vfgs_hw.c:170, as vfgs_hip_model_capture
+			return fail(9, "%s: parameter set %u: grain_scaling %d at depth %d: scale_shift out of range (vfgs_hw.c:170)", who, i, jobs[i].scale_shift + 6, 8 + s.bs);
+	}
+	if (int e = fw_prepare(s)) return e;
+	hipStream_t stream = pick_stream(stream_);
+	size_t largest = 0;      // a slab holds kFwModelChunk models of the largest image of this depth and format, whatever this chunk's forms are
+	for (int f = 0; f < 2; f++)      // (all one-pattern, all general: the mixed forms lie between)
+		largest = std::max(largest, (size_t)layout_of(s.csubx, s.csuby, !f, !f, d8).bytes);
+	const size_t table_bytes = sizeof(FwModelJob) * kFwModelChunk;
+	const size_t slab_bytes = table_bytes + kFwModelChunk * ((kModelRecordBytes + largest + 15) & ~(size_t)15);
+	std::vector<vfgs_hip_model*> made;
+	uint64_t launches = 0;
+	auto undo = [&](ModelSlab* empty) {
+		(void)hipStreamSynchronize(stream);     // (whatever was queued on the slabs is done before they go)
+		for (vfgs_hip_model* m : made) model_destroy(m);
+		if (empty) slab_destroy(empty);
+	};
+	for (unsigned c0 = 0; c0 < n; c0 += kFwModelChunk)
+	{
+		const unsigned cn = std::min<unsigned>(kFwModelChunk, n - c0);
+		// the oldest idle slab that is large enough, once its readers are done (normally long ago), else a new one
+		ModelSlab* sl = nullptr;
+		for (size_t i = 0; i < g_slabs_idle.size() && !sl; i++)
+			if (g_slabs_idle[i]->cap >= slab_bytes) { sl = g_slabs_idle[i]; g_slabs_idle.erase(g_slabs_idle.begin() + (long)i); }
+		hipError_t e = hipSuccess;
+		if (sl) e = sl->guard.wait_free();
+		else
+		{
+			sl = new ModelSlab;
+			e = hipMalloc((void**)&sl->dev, slab_bytes);
+			if (e == hipSuccess) { g_build_stats[4]++; e = hipHostMalloc((void**)&sl->stage, table_bytes, hipHostMallocDefault); }
+			sl->cap = slab_bytes;
+		}
+		size_t off = table_bytes;
+		for (unsigned k = 0; k < cn && e == hipSuccess; k++)
+		{
+			FwModelJob& j = jobs[c0 + k];
+			const int arg_shift = j.scale_shift;
+			j.scale_shift = arg_shift + 6 - s.bs;
+			bool one_y = lut_fits16(s.bs, j.scale_shift, j.slut[0]), one_c = lut_fits16(s.bs, j.scale_shift, j.slut[1]) && lut_fits16(s.bs, j.scale_shift, j.slut[2]);
+#ifdef VFGS_NO_ONE_PATTERN      // (image_form)
+			one_y = one_c = false;
+#endif
+			j.one_y = one_y; j.one_c = one_c;
+			const int ymin = j.legal ? 16 : 0, ymax = j.legal ? 235 : 255, cmax = j.legal ? 240 : 255;     // vfgs_set_legal_range
+			j.rec = ModelRecord{};
+			j.rec.lo2[0] = (uint32_t)(ymin << s.bs) * 0x10001u; j.rec.hi2[0] = (uint32_t)(ymax << s.bs) * 0x10001u;
+			j.rec.lo2[1] = (uint32_t)(ymin << s.bs) * 0x10001u; j.rec.hi2[1] = (uint32_t)(cmax << s.bs) * 0x10001u;
+			j.rec.pk_shift = j.scale_shift;
+			j.dst = sl->dev + off;
+			const size_t bytes = (size_t)kModelRecordBytes + (size_t)layout_of(s.csubx, s.csuby, one_y, one_c, d8).bytes;
+			off += (bytes + 15) & ~(size_t)15;
+			sl->stage[k] = j;
+		}
+		if (e == hipSuccess) e = hipMemcpyAsync(sl->dev, sl->stage, sizeof(FwModelJob) * cn, hipMemcpyHostToDevice, stream);
+		if (e == hipSuccess) e = launch(s.fw_const, (const FwModelJob*)sl->dev, (int)cn, s.csubx, s.csuby, d8, stream);
+		if (e == hipSuccess) e = sl->guard.uploaded(stream);
+		if (e != hipSuccess)
+		{
+			(void)hipGetLastError();
+			undo(sl);
+			return fail((int)e, "%s: chunk of %u models at %u -> %s", who, cn, c0, hipGetErrorString(e));
+		}
+		launches++;
+		for (unsigned k = 0; k < cn; k++)
+		{
+			const FwModelJob& j = jobs[c0 + k];
+			vfgs_hip_model* m = new vfgs_hip_model;
+			m->dev = j.dst;
+			m->bs = s.bs; m->csubx = s.csubx; m->csuby = s.csuby;
+			m->one_y = j.one_y != 0; m->one_c = j.one_c != 0;
+			m->scale_shift = j.scale_shift;
+			m->legal = j.legal != 0;
+			m->rec = j.rec;
+			m->bytes = (size_t)kModelRecordBytes + (size_t)layout_of(s.csubx, s.csuby, m->one_y, m->one_c, d8).bytes;
+			m->slab = sl;
+			sl->live++;
+			made.push_back(m);
+		}
+	}
+	for (unsigned i = 0; i < n; i++) { g_models.push_back(made[i]); out[i] = made[i]; }
+	g_build_stats[0]++; g_build_stats[1] += n; g_build_stats[2] += launches; g_build_stats[3] += launches;
+	return 0;
+}
 }
 
 namespace {
@@ -3226,7 +3365,7 @@ static int launch_list(ListCall& l)
 			for (unsigned k = 0; k < n; k++)
 			{
 				vfgs_hip_model* m = const_cast<vfgs_hip_model*>(models[f0 + k]);
-				HIP_TRY(m->guard.use(c.stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
+				HIP_TRY(model_guard(m).use(c.stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
 				ft.model[k] = m->dev;
 			}
 			mr.one_y = models[f0]->one_y; mr.one_c = models[f0]->one_c;
@@ -3447,6 +3586,22 @@ void vfgs_hip_model_release(vfgs_hip_model* m)
 	if (it == g_models.end()) return;      // NULL, released before, or gone with vfgs_hip_shutdown
 	g_models.erase(it);
 	if (g_states[0].inited) (void)ensure_init(-1);
+	if (ModelSlab* sl = m->slab)
+	{
+		// a built model: its bytes stay where they are until the slab's last model is released; the slab then is left as a whole
+		delete m;
+		if (--sl->live) return;
+		(void)sl->guard.leave();
+		g_slabs_idle.push_back(sl);
+		if (g_slabs_idle.size() > kSlabsIdleMax)
+		{
+			ModelSlab* old = g_slabs_idle.front();
+			g_slabs_idle.erase(g_slabs_idle.begin());
+			(void)old->guard.wait_free();      // (normally long complete)
+			slab_destroy(old);
+		}
+		return;
+	}
 	(void)m->guard.leave();                // an event behind everything queued so far on every stream that read the image
 	g_models_left.push_back(m);
 	if (g_models_left.size() > kModelsLeftMax)
@@ -3466,6 +3621,27 @@ int vfgs_hip_model_info(const vfgs_hip_model* m, int out[8])
 	const int v[8] = {8 + m->bs, m->csubx, m->csuby, m->one_y, m->one_c, m->scale_shift, m->legal, (int)m->bytes};
 	memcpy(out, v, sizeof v);
 	return 0;
+}
+
+int vfgs_hip_model_image(const vfgs_hip_model* m_, void* out, size_t cap, size_t* bytes)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (!model_live(m_)) return fail(41, "vfgs_hip_model_image: %s", m_ ? "the model was released" : "null model");
+	vfgs_hip_model* m = const_cast<vfgs_hip_model*>(m_);
+	if (bytes) *bytes = m->bytes;
+	if (cap < m->bytes || !out) return fail(6, "vfgs_hip_model_image: a buffer of %zu bytes, the model's record and image take %zu", out ? cap : (size_t)0, m->bytes);
+	if (int e = ensure_init(-1)) return e;
+	HIP_TRY(hipEventSynchronize(model_guard(m).upload_ev));     // (whatever stream the model was made on)
+	HIP_TRY(hipMemcpy(out, m->dev, m->bytes, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+void vfgs_hip_get_model_build_stats(uint64_t out[8])
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	for (int i = 0; i < 6; i++) out[i] = g_build_stats[i];
+	out[6] = vfgs::kFwModelChunk;
+	out[7] = 0;
 }
 
 int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const vfgs_hip_model* const* models,

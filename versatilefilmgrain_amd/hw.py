@@ -125,6 +125,10 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_model_release.argtypes = [vp]
     lib.vfgs_hip_model_release.restype = None
     lib.vfgs_hip_model_info.argtypes = [vp, C.POINTER(i)]
+    lib.vfgs_hip_model_image.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.vfgs_hip_get_model_build_stats.argtypes = [C.POINTER(C.c_uint64)]
+    lib.vfgs_hip_get_model_build_stats.restype = None
+    lib.vfgs_hip_models_from_afgs1.argtypes = [vp, u, C.POINTER(vp), vp]
     lib.vfgs_hip_add_grain_frame_list_models_dev.argtypes = [fp, fp, C.POINTER(vp), sp, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_sp_frame_list_models_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
@@ -197,7 +201,7 @@ EXPORTS = [
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
     "vfgs_hip_model_capture", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
-    "vfgs_hip_add_grain_sp_frame_list_models_dev",
+    "vfgs_hip_add_grain_sp_frame_list_models_dev", "vfgs_hip_model_image", "vfgs_hip_get_model_build_stats",
 ]
 
 
@@ -394,6 +398,35 @@ class VfgsHip:
         out = (C.c_int * 8)()
         self._ck(self.lib.vfgs_hip_model_info(m, out))
         return dict(zip(("depth", "csubx", "csuby", "one_y", "one_c", "scale_shift", "legal_range", "device_bytes"), out))
+
+    def models_from_afgs1(self, cfgs, stream=0):
+        """Models straight from AFGS1 parameter sets (fw.FgsAfgs1 objects), one kernel launch per 32 of them, at the programmed depth and chroma
+        format: handles like model_capture's, each what `fw.afgs1_chroma_mix(False); fw.init_afgs1(cfg); model_capture()` would give, with
+        the programmed state untouched.  The pictures' seeds are fw.afgs1_seed(cfg), for the list call.  VfgsHipError 42: a parameter set
+        vfgs_init_afgs1 would abort on (the message names its index), 9: grain_scaling out of range; nothing is built then."""
+        from . import fw
+        cfgs = list(cfgs)
+        if not cfgs:
+            return []
+        arr = (fw.FgsAfgs1 * len(cfgs))(*cfgs)
+        out = (C.c_void_p * len(cfgs))()
+        self._ck(self.lib.vfgs_hip_models_from_afgs1(arr, len(cfgs), out, stream))
+        return list(out)
+
+    def model_image(self, m):
+        """The model's 32-byte record and table image as the device holds them (bytes).  Synchronises; for tests and debugging."""
+        need = C.c_size_t(0)
+        rc = self.lib.vfgs_hip_model_image(m, None, 0, C.byref(need))
+        if rc != 6:
+            self._ck(rc)
+        buf = C.create_string_buffer(need.value)
+        self._ck(self.lib.vfgs_hip_model_image(m, buf, need.value, C.byref(need)))
+        return buf.raw
+
+    def model_build_stats(self):
+        out = (C.c_uint64 * 8)()
+        self.lib.vfgs_hip_get_model_build_stats(out)
+        return dict(zip(("calls", "models", "launches", "copies", "allocations", "frees", "models_per_launch"), out))
 
     def add_grain_frame_list_models_dev(self, src, dst, models, seeds, width, height, stride, cstride, stream=0):
         """The list call with a model per picture: frame f is grained as if models[f]'s state were programmed (and, with seeds,
