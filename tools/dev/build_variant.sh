@@ -12,7 +12,7 @@ pids=()
 "${CC[@]}" -DVFGS_KERNEL_DEPTH=10 -c $C/vfgs_kernel.hip -o $T/k10.o & pids+=($!)
 "${CC[@]}" -DVFGS_KERNEL_DEPTH=8 -c $C/vfgs_kernel.hip -o $T/k8.o & pids+=($!)
 "${CC[@]}" -DVFGS_KERNEL_DEPTH=12 -c $C/vfgs_kernel.hip -o $T/k12.o & pids+=($!)
-for f in vfgs_fw_kernel.hip vfgs_host.cpp vfgs_fw_host.cpp vfgs_cfg_host.cpp; do "${CC[@]}" -c $C/$f -o $T/${f%.*}.o & pids+=($!); done
+for f in vfgs_fw_kernel.hip vfgs_host.cpp vfgs_fw_host.cpp vfgs_cfg_host.cpp vfgs_model_build_host.cpp; do "${CC[@]}" -c $C/$f -o $T/${f%.*}.o & pids+=($!); done
 ok=1; for p in "${pids[@]}"; do wait $p || ok=0; done
 [ $ok = 1 ] && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/bin/$name.so $T/*.o && echo built tools/bin/$name.so
 rm -rf $T

@@ -1885,6 +1885,10 @@ int Launch::plan_grid()
 	const bool in_region = g_states[0].ov.active && (stream == g_states[0].ov.s[0] || stream == g_states[0].ov.s[1]);
 	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + (sp ? 1 : 2) * cext) >= (64u << 20)) ? 1 : 0;
 #endif
+	// ... one plane phase apart, but for the launch's last pair (vfgs_layout.h front_phase; grain_rw_kernel only, DESIGN.md 5.0 "a plane phase apart")
+	const vfgs::FrontPhase fp = vfgs::front_phase(a.lfronts, !sp && !p2sp && !mix && !mr, a.pd[0].wgs, a.pd[1].wgs, (int)nframes);
+	a.front_shift = fp.shift;
+	a.front_plain_from = fp.plain_from;
 	return 0;
 }
 

@@ -1245,8 +1245,10 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 	}
 	else
 	{
-		f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
-		r = (int)(blockIdx.x >> a.lfronts);
+		// (the odd front of a pair runs one plane phase behind the even one -- chroma beside luma on every CU: vfgs_layout.h front_task, DESIGN.md 5.0 "a plane phase apart")
+		const FrontTask t = front_task(blockIdx.x, blockIdx.y, a.lfronts, a.pd[0].wgs + 2 * a.pd[1].wgs, a.front_shift, a.front_plain_from);
+		f = t.f;
+		r = t.r;
 	}
 	if (f >= a.nframes) return;
 	if (r < a.pd[0].wgs)
@@ -1941,6 +1943,8 @@ static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const Ke
 	if (k.wide != (a.nblk > kTileBlocks)) return false;
 	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return false;
 	if ((a.listed != 0) != (list != nullptr) || (list && a.nframes > kListFrames)) return false;
+	// the phase between two frame fronts: grain_rw_kernel's alone, a rotation inside the frame's tasks
+	if (a.front_shift != 0 && (f != Family::rw || k.persist || a.lfronts != 1 || a.front_shift < 0 || a.front_shift >= a.pd[0].wgs + 2 * a.pd[1].wgs)) return false;
 	if (a.models_kernel)
 	{
 		// a model per frame: listed frames, every frame with a model image

@@ -63,13 +63,20 @@ constexpr int kBlock = 16;       // luma samples per grain block
 #ifndef VFGS_RW_CONSEC
 #define VFGS_RW_CONSEC 0      // 1 = a wave's rows are consecutive, 0 = the waves of a workgroup take every kWavesPerWG-th row
 #endif
+// Two frame fronts in one launch (KernelArgs::lfronts == 1): 1 = the odd front of a pair starts one plane phase later (Cb, Cr, Y), so that luma
+// and chroma workgroups share the CUs; the launch's last pair keeps the order of memory (front_phase / front_task below).  0 = both fronts
+// in the order of memory, 2 = the last pair rotated as well.  4320p 10-bit 4:2:0 fgs_sei x 8: 1 is worth 1.5 % and 2.2 % on two boxes against
+// a parent-to-parent spread of 0.01 % and 0.24 %, 2 half of that (the launch drains on luma workgroups); profiles/front_phase.json.
+#ifndef VFGS_FRONT_PHASE
+#define VFGS_FRONT_PHASE 1
+#endif
 
 // The product is built with every knob at its default (versatilefilmgrain_amd/build.py passes none).  The developer tools that
 // time variants (tools/dev/build_variant.sh, tools/gpu_variants.sh) define VFGS_DEV_BUILD; without it any
 // other value is a build error, so a stray -D cannot produce a library that silently runs something else -- and a
 // developer build says so at run time (vfgs_hip_dev_build(), refused by versatilefilmgrain_amd.hw unless asked for).
 #if !defined(VFGS_DEV_BUILD)
-#if VFGS_WAVES != 4 || VFGS_WG_PER_CU != 4 || VFGS_RING != 4 || VFGS_RING_ONE10 != 4 || VFGS_RING_PK != 2 || VFGS_RING_NARROW10 != 2 || VFGS_ONE10_WG_PER_CU != 4 || VFGS_ONE8_WG_PER_CU != 0 || VFGS_SCHED_FENCE != 1 || VFGS_LDAUX_ALIGNED != 2 || VFGS_STAUX_ALIGNED != 2 || VFGS_RW_CONSEC != 0 || \
+#if VFGS_WAVES != 4 || VFGS_WG_PER_CU != 4 || VFGS_RING != 4 || VFGS_RING_ONE10 != 4 || VFGS_RING_PK != 2 || VFGS_RING_NARROW10 != 2 || VFGS_ONE10_WG_PER_CU != 4 || VFGS_ONE8_WG_PER_CU != 0 || VFGS_SCHED_FENCE != 1 || VFGS_LDAUX_ALIGNED != 2 || VFGS_STAUX_ALIGNED != 2 || VFGS_RW_CONSEC != 0 || VFGS_FRONT_PHASE != 1 || \
     defined(VFGS_NO_FRONTS) || defined(VFGS_NO_LOOKAHEAD) || defined(VFGS_NO_ONE_PATTERN) || defined(VFGS_NO_PK16) || defined(VFGS_PK_NO_READ2) || defined(VFGS_PK_WAVES) || defined(VFGS_ONE10_WAVES) ||  defined(VFGS_RW_WG_BYTES) || defined(VFGS_RW_MIN_FILL_PCT) || defined(VFGS_PERSIST_MIN_TASKS) || defined(VFGS_PERSIST_MAX_WG_KB)
 #error "libvfgs_hip: a tuning knob differs from the shipped configuration; developer variants must define VFGS_DEV_BUILD"
 #endif
@@ -315,8 +322,41 @@ struct KernelArgs {
 	                          //    component's row -- the destination is such a UV plane: dst[1] == dst[2], pd[1].dpitch its row pitch and pd[1].drowbytes ONE
 	                          //    component's bytes of its row (the row holds twice as many); pd[0].dpitch / drowbytes: the destination's luma row
 	uint32_t sp_shift2;       // ... 16-bit containers: the samples sit this many bits up (P010: 6, P012: 4), in both halves of the dword (a packed 16-bit shift each way)
+	// The phase between the two frame fronts (front_phase / front_task below; both zero = the fronts in step, every kernel but grain_rw_kernel)
+	int front_shift;          // tasks by which the odd front of a pair of frames is rotated: it runs task (r + front_shift) mod per-frame tasks where the even front runs task r
+	int front_plain_from;     // ... the first group of frames (blockIdx.y) that is NOT rotated
 };
-static_assert(sizeof(KernelArgs) == 304, "the frame table follows KernelArgs in the kernel arguments: a new size moves what every kernel loads from it");
+static_assert(sizeof(KernelArgs) == 312, "the frame table follows KernelArgs in the kernel arguments: a new size moves what every kernel loads from it");
+
+// WHICH task a workgroup of a launch's grid (vfgs_kernel.hip grid_of) runs: frame f, task r of the frame's per_frame tasks (luma, Cb, Cr in
+// the order of memory).  x = (task, front of a group of 2^lfronts frames), y = group of frames; f may lie behind the launch's last frame
+// (an odd number of frames: the kernel returns).  The ODD front of a group in front of front_plain_from runs its tasks rotated by front_shift:
+// a bijection of the frame's tasks, so every (f, r) is still dealt out exactly once, and no kernel relies on the order of workgroups.
+// (constexpr: host and device code call it alike, like every function of this header)
+struct FrontTask { int f, r; };
+constexpr FrontTask front_task(const unsigned bx, const unsigned by, const int lfronts, const int per_frame, const int front_shift, const int front_plain_from)
+{
+	const unsigned front = bx & ((1u << lfronts) - 1);
+	FrontTask t{(int)(by << lfronts) + (int)front, (int)(bx >> lfronts)};
+	if (VFGS_FRONT_PHASE != 0 && front_shift != 0 && (front & 1) && (int)by < front_plain_from)
+	{
+		t.r += front_shift;
+		if (t.r >= per_frame) t.r -= per_frame;
+	}
+	return t;
+}
+
+// The host's rule for the two fields (vfgs_host.cpp Launch::plan_grid).  Two fronts of the planar row walk: the odd front starts at the first
+// chroma task (Cb, Cr, Y) in every group but the launch's last, which keeps the order of memory -- the launch then drains on short chroma
+// workgroups, not on luma workgroups that take several times as long.  A launch of one group is the launch of always.
+struct FrontPhase { int shift, plain_from; };
+constexpr FrontPhase front_phase(const int lfronts, const bool rw_family, const int wgs_y, const int wgs_c, const int nframes)
+{
+	if (VFGS_FRONT_PHASE == 0 || lfronts != 1 || !rw_family || wgs_y <= 0 || wgs_c <= 0) return FrontPhase{0, 0};
+	const int groups = (nframes + 1) >> 1;
+	const int plain_from = VFGS_FRONT_PHASE == 2 ? groups : groups - 1;
+	return plain_from > 0 ? FrontPhase{wgs_y, plain_from} : FrontPhase{0, 0};
+}
 
 // WHICH kernel serves a launch: the kernel family and its template arguments.  The host forms one key per call (vfgs_host.cpp Launch::key), the
 // launcher instantiates and dispatches from kernel_exists() (vfgs_kernel.hip launch_key), the launch record names the kernel and its LDS with
