@@ -48,6 +48,17 @@ def test_one_kernel_has_exactly_one_key(keys):
     assert [sum(1 for n in names if n.split("<")[1].split(",")[0] == d) for d in ("8", "10", "12")] == [72, 134, 120]
 
 
+def test_the_committed_key_list_is_the_tables(keys):
+    """tests/golden/kernel_keys.txt -- what tests/test_gpu_kernel_keys.py launches key by key, without a compiler -- is this program's output
+    line for line, and every key it prints has a launch recipe (tests/kernel_key_cases.py) whose program takes the key's form"""
+    import kernel_key_cases as K
+    import model_programs as MP
+    assert K.fixture() == keys, ("regenerate tests/golden/kernel_keys.txt from tests/kernel_keys/kernel_keys.cpp", sorted(set(K.fixture()) ^ set(keys)))
+    for name, _ in keys:
+        c = K.case_for(name)
+        assert K.key_name(c.key) == name and MP.expected_form(MP.program(c.program), c.key.wide) == (c.key.oney, c.key.onec), (name, c.program)
+
+
 def test_the_code_objects_hold_the_keys_and_nothing_else(keys, kernels):
     have = [r["name"] for r in kernels]
     assert len(have) == len(set(have)), sorted(n for n in set(have) if have.count(n) > 1)
