@@ -383,10 +383,10 @@ int  vfgs_hip_model_info(const vfgs_hip_model* m, int out[8]);
  * (may be NULL) = their size = out[7] of vfgs_hip_model_info.  Synchronises (it waits for the work that made the model, on whatever stream);
  * for tests and debugging, like vfgs_hip_get_pattern.  41: a null or released handle; 6: `cap` is smaller than the size (or `out` is NULL),
  * with *bytes set to the size needed.  Serves captured models and models built from parameter sets (vfgs_hip_models_from_afgs1,
- * vfgs_hip_fw.h) alike. */
+ * vfgs_hip_models_from_sei, vfgs_hip_fw.h) alike. */
 int  vfgs_hip_model_image(const vfgs_hip_model* m, void* out, size_t cap, size_t* bytes);
 
-/* Bookkeeping of vfgs_hip_models_from_afgs1 (vfgs_hip_fw.h), in the style of vfgs_hip_get_seeded_stream_stats: out[8] = { calls that built,
+/* Bookkeeping of vfgs_hip_models_from_afgs1 and vfgs_hip_models_from_sei together (vfgs_hip_fw.h), in the style of vfgs_hip_get_seeded_stream_stats: out[8] = { calls that built,
  * models built, kernel launches, copies queued, device allocations (one slab each, with its pinned job table), device frees, models per
  * launch (the constant), 0 }.  A refused call changes none of them; in the steady state of build / grain / release the allocations and frees
  * stand still. */

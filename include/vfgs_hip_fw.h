@@ -125,6 +125,37 @@ unsigned int vfgs_hip_afgs1_seed(const fgs_afgs1* cfg);
 struct vfgs_hip_model;
 int vfgs_hip_models_from_afgs1(const fgs_afgs1* cfgs, unsigned n, struct vfgs_hip_model** out, void* stream);
 
+/* ... AND FROM FGC SEI MESSAGES.  A VVC / HEVC player that receives an FGC SEI with a picture (the reference CLI's `-c <poc>:<file>`) gets its
+ * models the same way.  The call works at the programmed depth, chroma format AND legal range (vfgs_set_depth, vfgs_set_chroma_subsampling,
+ * vfgs_set_legal_range: fgs_sei carries no range and vfgs_init_sei sets none); out[i] is a live model that no call taking models -- the two
+ * list calls with a model per picture, vfgs_hip_model_info, vfgs_hip_model_image, vfgs_hip_model_release -- can tell apart from the result of
+ *     vfgs_hip_reset_state(); vfgs_set_depth; vfgs_set_chroma_subsampling; vfgs_set_legal_range;
+ *     vfgs_init_sei(&cfgs[i]); vfgs_hip_model_capture(&out[i], stream);
+ * "From a reset state" makes this exact for every byte in every form: a general-form image holds the generated slots 0..np-1 of each list
+ * and zeros elsewhere.  The form follows the derived tables as capture's does: luma is one-pattern iff its pattern LUT selects one slot for
+ * all 256 intensities and (8 bit) its scale LUT fits the packed 16-bit form; chroma iff Cb's LUT and Cr's LUT are each uniform -- possibly
+ * on different slots -- and both scale LUTs fit; a uniform slot the list does not hold (an absent component, the unused entry the
+ * reference's pattern search can match) is the zero pattern.  The reference firmware's quirks are those vfgs_init_sei restates.
+ * The PROGRAMMED STATE IS UNTOUCHED: host mirror, device pattern banks, pending pattern requests, table images, depth, format and range, the
+ * four seed registers, the chroma mix and its switch are what they were.  A model carries no mix; an SEI carries no seed: the seed stays
+ * the caller's (`seeds` of the list call, or the running sequence).
+ * One kernel serves up to 32 models (one workgroup each: every pattern of the message -- up to 8 luma and 8 chroma -- made in LDS, then the
+ * whole record + image written from there), so a call queues ONE copy (the job table) and ONE launch per 32 models; the models of a chunk
+ * share one device allocation from the pool of vfgs_hip_models_from_afgs1, and vfgs_hip_get_model_build_stats counts both calls in the same
+ * counters: no allocation and no free in the steady state of build / grain / release.  Asynchronous on `stream`; a first use on another
+ * stream waits by event; inside an overlap region pass the region's stream.
+ * REFUSALS replace vfgs_init_sei's aborts and out-of-bounds reads.  A refused call builds nothing, sets out[0..n) to NULL, queues nothing and
+ * changes no statistic; the message names the index and the cause (all messages are examined for 42 first, then for 9):
+ *   41  out == NULL, or cfgs == NULL (n > 0)
+ *   42  num_intensity_intervals[c] > 256 for a component whose comp_model_present_flag[c] is set (the arrays hold 256);
+ *       model_id != 0 with log2_scale_factor outside 1..15 (the pattern job is refused there and vfgs_init_sei aborts)
+ *    9  the scale shift that vfgs_set_scale_shift(log2_scale_factor - (model_id ? 1 : 0)) would store is out of range at the programmed
+ *       depth (vfgs_hw.c:170), exactly as vfgs_hip_model_capture refuses it: the argument outside 2..7
+ * Everything else is accepted and behaves as vfgs_init_sei does: any non-zero model_id is the auto-regressive model, cut-offs of any int16
+ * value clamp as the pattern generator clamps them, more than 8 distinct parameter sets, unsorted or overlapping intervals, gaps and absent
+ * components (luma included) give what the reference firmware gives.  n == 0 is no call at all and returns 0. */
+int vfgs_hip_models_from_sei(const fgs_sei* cfgs, unsigned n, struct vfgs_hip_model** out, void* stream);
+
 /* One grain pattern to be generated on the device into pattern slot `index`. */
 typedef struct vfgs_hip_pattern_job {
 	int32_t kind;       /* 0: frequency filtered (vfgs_fw.c:362-408), 1: auto-regressive (vfgs_fw.c:410-502) */

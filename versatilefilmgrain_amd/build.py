@@ -15,12 +15,12 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libvfgs_hip.so"
 SOURCES = [CSRC / "vfgs_kernel.hip", CSRC / "vfgs_fw_kernel.hip", CSRC / "vfgs_host.cpp", CSRC / "vfgs_fw_host.cpp", CSRC / "vfgs_cfg_host.cpp",
-           CSRC / "vfgs_model_build_host.cpp"]
+           CSRC / "vfgs_model_build_host.cpp", CSRC / "vfgs_model_build_sei_host.cpp"]
 # bench-only streaming kernels (the copy ceiling bench.py reports): a library of their own, outside the product and its ABI
 DIAG_SRC = PKG.parent / "tools" / "bench_diag.hip"
 DIAG_LIB = PKG.parent / "tools" / "bin" / "libvfgs_bench_diag.so"
 FW_TABLES = CSRC / "fw_tables.bin"   # model constants, linked into the library as data (oracle/dump_fw_tables.c)
-HEADERS = [CSRC / "vfgs_layout.h", CSRC / "vfgs_fw_layout.h", CSRC / "vfgs_model_build.h", CSRC / "vfgs_fw_afgs1.h", FW_TABLES,
+HEADERS = [CSRC / "vfgs_layout.h", CSRC / "vfgs_fw_layout.h", CSRC / "vfgs_model_build.h", CSRC / "vfgs_fw_afgs1.h", CSRC / "vfgs_fw_sei.h", FW_TABLES,
            PKG.parent / "include" / "vfgs_hip.h", PKG.parent / "include" / "vfgs_hip_fw.h"]
 ARCH = "gfx950"
 

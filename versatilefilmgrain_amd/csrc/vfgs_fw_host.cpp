@@ -18,10 +18,11 @@
 #include "../../include/vfgs_hip.h"
 #include "../../include/vfgs_hip_fw.h"
 #include "vfgs_fw_afgs1.h"
+#include "vfgs_fw_sei.h"
 
 namespace {
 
-constexpr int kMaxPatterns = 8;   // VFGS_MAX_PATTERNS, vfgs_hw.h:49
+constexpr int kMaxPatterns = vfgs::kSeiMaxPatterns;
 
 [[noreturn]] void fw_die(const char* fmt, ...)
 {
@@ -52,68 +53,10 @@ void generate(const vfgs_hip_pattern_job* jobs, int n)
 
 // ---- SEI -------------------------------------------------------------------------------
 
-// The list of distinct patterns of one bank.  An entry is the position of an interval's model
-// values in comp_model_value viewed as one flat int16 array (vfgs_fw.c:545: 6*(k + 256*c)).
-struct PatternList {
-	int n = 0;
-	bool used[kMaxPatterns] = {};
-	int flat[kMaxPatterns] = {};
-	unsigned char lower[kMaxPatterns] = {};   // lower intensity bound the entry was created from (sort key)
-};
-
-// Values 1..5 of an entry, i.e. everything but the scale factor (vfgs_fw.c:504-515).
-// QUIRK: the reference initialises unused entries to ~0 and still compares against them; with
-// its pointer arithmetic an unused entry reads elements -1+1 .. -1+5 of the flat array, that is
-// the FIRST five numbers of the luma component's first interval.  Reproduced.
-const int16_t* entry_tail(const fgs_sei* cfg, const PatternList& pl, int i)
-{
-	const int16_t* base = &cfg->comp_model_value[0][0][0];
-	return pl.used[i] ? base + pl.flat[i] + 1 : base;
-}
-
-int find_pattern(const fgs_sei* cfg, const PatternList& pl, int flat)
-{
-	const int16_t* want = &cfg->comp_model_value[0][0][0] + flat + 1;
-	for (int i = 0; i < kMaxPatterns; i++)
-		if (!memcmp(entry_tail(cfg, pl, i), want, (SEI_MAX_MODEL_VALUES - 1) * sizeof(int16_t)))
-			return i;
-	return kMaxPatterns;
-}
-
-void collect_patterns(const fgs_sei* cfg, int c, PatternList& pl)
-{
-	// vfgs_fw.c:540-572: new parameter sets join the list, which stays sorted by the lower bound
-	for (int k = 0; k < cfg->num_intensity_intervals[c]; k++)
-	{
-		const int flat = SEI_MAX_MODEL_VALUES * (k + 256 * c);
-		if (find_pattern(cfg, pl, flat) != kMaxPatterns || pl.n >= kMaxPatterns)
-			continue;
-		const unsigned char a = cfg->intensity_interval_lower_bound[c][k];
-		int at = pl.n;
-		while (at > 0 && pl.lower[at - 1] > a)
-		{
-			pl.lower[at] = pl.lower[at - 1];
-			pl.flat[at] = pl.flat[at - 1];
-			at--;
-		}
-		pl.lower[at] = a;
-		pl.flat[at] = flat;
-		pl.used[pl.n] = true;   // entries 0..n are the used ones; the sort only moves values
-		pl.n++;
-	}
-}
-
-// SEI auto-regressive model: the six model values become a 4x7 tap matrix (vfgs_fw.c:427-436)
-void sei_ar_taps(const int16_t* v, int scale, int16_t coef[28])
-{
-	memset(coef, 0, 28 * sizeof(int16_t));
-	auto at = [&](int row, int col) -> int16_t& { return coef[row * 7 + col]; };
-	at(3, 2) = v[1];                                           // left
-	at(2, 3) = (int16_t)((v[1] * v[4]) >> scale);              // top
-	at(2, 2) = at(2, 4) = (int16_t)((v[3] * v[4]) >> scale);   // top-left, top-right
-	at(3, 1) = v[5];                                           // two to the left
-	at(1, 3) = (int16_t)((int32_t)((uint32_t)v[5] * (uint32_t)v[4] * (uint32_t)v[4]) >> (2 * scale));   // two up
-}
+// the list of distinct patterns, the tap matrix and the LUT fill: vfgs_fw_sei.h, shared with vfgs_hip_models_from_sei
+using vfgs::PatternList;
+using vfgs::collect_patterns;
+using vfgs::sei_ar_taps;
 
 void sei_jobs(const fgs_sei* cfg, const PatternList& pl, int chroma, vfgs_hip_pattern_job* jobs, int& n)
 {
@@ -144,31 +87,7 @@ void sei_jobs(const fgs_sei* cfg, const PatternList& pl, int chroma, vfgs_hip_pa
 void sei_luts(const fgs_sei* cfg, const PatternList& pl, int c, unsigned char slut[256])
 {
 	unsigned char plut[256];
-	if (cfg->comp_model_present_flag[c])
-	{
-		memset(plut, 255, sizeof plut);
-		for (int k = 0; k < cfg->num_intensity_intervals[c]; k++)
-		{
-			const int a = cfg->intensity_interval_lower_bound[c][k];
-			const int b = cfg->intensity_interval_upper_bound[c][k];
-			const int i = find_pattern(cfg, pl, SEI_MAX_MODEL_VALUES * (k + 256 * c));
-			for (int l = a; l <= b; l++)
-			{
-				slut[l] = (unsigned char)cfg->comp_model_value[c][k][0];
-				if (i < kMaxPatterns)
-					plut[l] = (unsigned char)(i << 4);
-			}
-		}
-		// intensities outside every interval repeat the pattern below them (vfgs_fw.c:625-633)
-		unsigned char last = 0;
-		for (int k = 0; k < 256; k++)
-		{
-			if (plut[k] == 255) plut[k] = last;
-			else last = plut[k];
-		}
-	}
-	else
-		memset(plut, 0, sizeof plut);
+	vfgs::sei_fill_luts(cfg, pl, c, slut, plut);
 	vfgs_set_scale_lut(c, slut);
 	vfgs_set_pattern_lut(c, plut);
 }

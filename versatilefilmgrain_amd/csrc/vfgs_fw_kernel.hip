@@ -165,7 +165,7 @@ __device__ inline int mad24(int a, int b, int c)
 	return d;
 }
 
-// Caller: one instantiation per kernel that runs the recursion (0: fw_ar_kernel, 1: fw_models_kernel).  The optimiser propagates what a
+// Caller: one instantiation per kernel that runs the recursion (0: fw_ar_kernel, 1: fw_models_kernel, 2: fw_sei_build_kernel).  The optimiser propagates what a
 // function's ONLY caller passes into it before it inlines; with one instantiation for both, fw_ar_kernel would come out with other -- equivalent
 // -- instructions than the ones that were measured (tools/dev/compare_code_objects.py).
 template <int L, int Caller = 0>
@@ -451,6 +451,270 @@ __global__ __launch_bounds__(256) void fw_models_kernel(const FwConstants* __res
 }
 
 // ---------------------------------------------------------------------------------------
+// Whole models from FGC SEI messages (vfgs_hip_models_from_sei, vfgs_model_build.h): one 1024-thread workgroup per model, a chunk of
+// models per launch.  What the capture path does in up to 16 pattern jobs through the global banks, a bank copy, a host-built image, an
+// upload and fw_patch_tables happens here between LDS and the model's own buffer; the bytes are those of vfgs_init_sei +
+// vfgs_hip_model_capture from a reset state, in every form.
+//
+//   frequency filtered: every pattern of a plane type draws the same noise and uses the same basis, so Gaussian table, stream words and
+//                       basis (Dt, Dp) are staged once per plane type; per pattern: the masked fill of Bt, the sdot4 pass, the sdot2 pass
+//                       with the clip -- fw_ff_kernel's body as a device function of this kernel's own -- into an LDS staging array.
+//                       Only the patterns the image holds are made: all of a list in the general form, the selected slot(s) in the
+//                       one-pattern form, and outside 4:2:0 the last luma pattern wherever a chroma pattern is made (below).
+//   auto-regressive   : one wavefront per pattern, up to 16 recursions side by side in arenas of fw_models_kernel's sizes; the SEI taps
+//                       reach 2 (sei_ar_taps), one instantiation ar_rows<2, 2> of this kernel's own.
+// Then all 16 wavefronts write record, zero fill, LUTs and banks.  A chroma slot outside 4:2:0 is the reference's shared 64x64 scratch
+// buffer read with pitch 64/csuby: the raw 32x32 pattern, then the tail of luma pattern np_luma - 1 of the same message (zero without
+// one) -- fw_commit_chroma's last_luma, taken from LDS.
+//
+// one frequency-filtered pattern of an NxN plane type: Bt is refilled, X rewritten, out[j * N + i] receives the clipped samples.  Holds
+// two barriers; the caller keeps one between the last pattern and whatever rewrites Dt / Dp.
+template <int N>
+__device__ __forceinline__ void sei_ff_pattern(int8_t* Bt, const int8_t* Dt, int16_t* X, const uint32_t* Dp, const int8_t* G, const uint32_t* W,
+                                               const int cut_h, const int cut_v, int8_t* out, const int tid)
+{
+	constexpr int BP = 68;
+	constexpr int gw = N / 16;
+	const int fh = min(gw * (cut_h + 1), N);   // vfgs_fw.c:366-367, :389-390
+	const int fv = min(gw * (cut_v + 1), N);
+	if (tid < N * 16)
+	{
+		const int l = tid >> 4, k = (tid & 15) * gw;
+		const int r = noise_index(W, tid);
+		const bool in = k < fh && l < fv;
+		for (int j = 0; j < gw; j++)
+			Bt[(k + j) * BP + l] = (in && (tid || j)) ? G[(r + j) & 2047] : (int8_t)0;   // (tid || j): no DC (vfgs_fw.c:383, :406)
+	}
+	__syncthreads();
+	// each thread owns column i and rows j0, j0 + jstep, ... (4 outputs for N = 64, 1 for N = 32)
+	constexpr int jstep = 1024 / N, per = N * N / 1024;
+	const int i = tid % N, j0 = tid / N;
+	int acc[per];
+#pragma unroll
+	for (int m = 0; m < per; m++) acc[m] = N == 64 ? 256 : 128;   // vfgs_fw.c:307, :340
+	for (int k4 = 0; k4 < (fv + 3) / 4; k4++)
+	{
+		const int b = *(const int*)(Bt + i * BP + 4 * k4);
+#pragma unroll
+		for (int m = 0; m < per; m++)
+			acc[m] = __builtin_amdgcn_sdot4(*(const int*)(Dt + (j0 + m * jstep) * BP + 4 * k4), b, acc[m], false);
+	}
+#pragma unroll
+	for (int m = 0; m < per; m++) X[(j0 + m * jstep) * 64 + i] = (int16_t)(acc[m] >> (N == 64 ? 9 : 8));
+	__syncthreads();
+#pragma unroll
+	for (int m = 0; m < per; m++) acc[m] = 256;                   // vfgs_fw.c:318, :351
+	for (int k2 = 0; k2 < (fh + 1) / 2; k2++)
+	{
+		const s16x2_t d = __builtin_bit_cast(s16x2_t, Dp[k2 * 64 + i]);
+#pragma unroll
+		for (int m = 0; m < per; m++)
+			acc[m] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2_t, *(const uint32_t*)(X + (j0 + m * jstep) * 64 + 2 * k2)), d, acc[m], false);
+	}
+#pragma unroll
+	for (int m = 0; m < per; m++) out[(j0 + m * jstep) * N + i] = (int8_t)clip127(acc[m] >> 9);
+}
+
+// one bank of the one-pattern form from a pattern v(row, column): bytes -- int16 values in the packed 16-bit form -- and the negated copy
+template <typename F>
+__device__ __forceinline__ void sei_write_one(uint8_t* bank, int rs, int neg, int rows, int cols, bool pk16, int tid, F v)
+{
+	if (pk16)
+		for (int o = tid; o < rows * cols / 2; o += 1024)
+		{
+			const int r = o / (cols / 2), x = 2 * (o % (cols / 2));
+			const int a = v(r, x), b = v(r, x + 1);
+			*(uint32_t*)(bank + r * rs + 2 * x) = (uint32_t)(uint16_t)a | ((uint32_t)(uint16_t)b << 16);
+			*(uint32_t*)(bank + neg + r * rs + 2 * x) = (uint32_t)(uint16_t)-a | ((uint32_t)(uint16_t)-b << 16);
+		}
+	else
+		for (int o = tid; o < rows * cols / 4; o += 1024)
+		{
+			const int r = o / (cols / 4), x = 4 * (o % (cols / 4));
+			uint32_t p = 0, n = 0;
+			for (int q = 0; q < 4; q++)
+			{
+				const int a = v(r, x + q);
+				p |= (uint32_t)(uint8_t)a << (8 * q);
+				n |= (uint32_t)(uint8_t)-a << (8 * q);
+			}
+			*(uint32_t*)(bank + r * rs + x) = p;
+			*(uint32_t*)(bank + neg + r * rs + x) = n;
+		}
+}
+
+__global__ __launch_bounds__(1024) void fw_sei_build_kernel(const FwConstants* __restrict__ k, const FwSeiJob* __restrict__ jobs, int csubx, int csuby, int depth8)
+{
+	const FwSeiJob& jb = jobs[blockIdx.x];
+	__shared__ __attribute__((aligned(16))) int8_t lds[kFwSeiLdsBytes];
+	const int tid = threadIdx.x;
+	const bool ar = jb.kind != 0;
+	const bool one_y = jb.one_y != 0, one_c = jb.one_c != 0;
+	const int npy = jb.np_luma, npc = jb.np_chroma;                      // 0..8
+	const int slot_y = jb.slot[0], slot_cb = jb.slot[1], slot_cr = jb.slot[2];     // (>= 0 where the component is one-pattern)
+
+	// where the finished patterns lie: luma sample (slot, r, x) = ypat[slot * ysl + r * yp + x], raw chroma sample i of slot = cpat[slot * csl + (i >> 5) * cp + (i & 31)]
+	const int8_t *ypat, *cpat;
+	int ysl, yp, csl, cp;
+	if (!ar)
+	{
+		int8_t* const stage_y = lds;                         // [8][64][64]
+		int8_t* const stage_c = lds + 8 * 4096;              // [8][32][32]
+		int8_t* const Bt = stage_c + 8 * 1024;
+		int8_t* const Dt = Bt + 64 * 68;
+		int16_t* const X = (int16_t*)(Dt + 64 * 68);
+		uint32_t* const Dp = (uint32_t*)(X + 64 * 64);
+		int8_t* const G = (int8_t*)(Dp + 32 * 64);
+		uint32_t* const W = (uint32_t*)(G + 2048);           // [2][40]: seed indices 0 (luma) and 1 (chroma), vfgs_fw.c:369, :392
+		static_assert(8 * 4096 + 8 * 1024 + 2 * 64 * 68 + 64 * 64 * 2 + 32 * 64 * 4 + 2048 + 2 * 40 * 4 == kFwSeiLdsFf, "vfgs_model_build.h states the layout");
+		ypat = stage_y; ysl = 4096; yp = 64;
+		cpat = stage_c; csl = 1024; cp = 32;
+		// the patterns the image holds
+		uint32_t need_y = one_y ? (slot_y < npy ? 1u << slot_y : 0u) : (1u << npy) - 1u;
+		const uint32_t need_c = one_c ? ((slot_cb < npc ? 1u << slot_cb : 0u) | (slot_cr < npc ? 1u << slot_cr : 0u)) : (1u << npc) - 1u;
+		if (!(csubx == 2 && csuby == 2) && need_c && npy > 0) need_y |= 1u << (npy - 1);     // the tail of the scratch buffer
+		if (tid < 512) ((uint32_t*)G)[tid] = ((const uint32_t*)k->gauss)[tid];
+		if (tid < 80) W[tid] = k->stream[tid / 40][tid % 40];
+		const int8_t* D = &k->dct[0][0];
+		for (int pt = 0; pt < 2; pt++)
+		{
+			const uint32_t need = pt ? need_c : need_y;
+			if (!need) continue;
+			const int N = pt ? 32 : 64, dstep = 64 / N;      // the 32-point basis is every other row of the 64-point one (vfgs_fw.c:343,354)
+			// basis: one (k, j-quad) dword of D per thread -> four bytes of Dt, one (k-pair, i) entry of Dp per thread pair (fw_ff_kernel)
+			if (tid < N * 16)
+			{
+				const int kk = tid >> 4, j4 = (tid & 15) * 4;
+				const uint32_t d = *(const uint32_t*)(D + kk * dstep * 64 + j4);
+				for (int q = 0; q < 4; q++)
+					Dt[(j4 + q) * 68 + kk] = (int8_t)(d >> (8 * q));
+			}
+			for (int o = tid; o < (N / 2) * N; o += 1024)
+			{
+				const int k2 = o / N, i = o % N;
+				const int lo = D[(2 * k2) * dstep * 64 + i], hi = D[(2 * k2 + 1) * dstep * 64 + i];
+				Dp[k2 * 64 + i] = (uint32_t)(uint16_t)(int16_t)lo | ((uint32_t)(uint16_t)(int16_t)hi << 16);
+			}
+			__syncthreads();
+			for (int p = 0; p < kSlots; p++)
+			{
+				if (!(need >> p & 1)) continue;
+				if (pt) sei_ff_pattern<32>(Bt, Dt, X, Dp, G, W + 40, jb.pat[8 + p][0], jb.pat[8 + p][1], stage_c + p * 1024, tid);
+				else sei_ff_pattern<64>(Bt, Dt, X, Dp, G, W, jb.pat[p][0], jb.pat[p][1], stage_y + p * 4096, tid);
+			}
+			__syncthreads();
+		}
+	}
+	else
+	{
+		// guard zones as in fw_models_kernel: 256 bytes in front of every buffer, 128 behind; a chroma arena covers the 64 rows its wavefront's lanes read
+		constexpr int kArGuardLo = 256;
+		int8_t* const arena_y = lds;                                   // [8] kFwArenaLuma
+		int8_t* const arena_c = lds + 8 * kFwArenaLuma;                // [8] kFwArenaChroma
+		int8_t* const G = arena_c + 8 * kFwArenaChroma;
+		uint32_t* const W = (uint32_t*)(G + 2048);                     // [2][kFwStreamWords]
+		static_assert((8 * kFwArenaLuma + 8 * kFwArenaChroma) % 16 == 0 && 8 * kFwArenaLuma + 8 * kFwArenaChroma + 2048 + 2 * kFwStreamWords * 4 == kFwSeiLdsAr, "vfgs_model_build.h states the layout");
+		ypat = arena_y + kArGuardLo + 82 * 9 + 9; ysl = kFwArenaLuma; yp = 82;        // the crops (vfgs_fw.c:498-501): 64x64 at (9, 9), 32x32 at (6, 6)
+		cpat = arena_c + kArGuardLo + 44 * 6 + 6; csl = kFwArenaChroma; cp = 44;
+		if (tid < 512) ((uint32_t*)G)[tid] = ((const uint32_t*)k->gauss)[tid];
+		if (tid < 2 * kFwStreamWords) W[tid] = (&k->stream[0][0])[tid];
+		__syncthreads();
+		// the noise term of every sample (vfgs_fw.c:492-493 with shift 1, vfgs_fw.c:606): the same for every pattern of a plane type
+		for (int n = tid; n < 82 * 73; n += 1024)
+		{
+			const int8_t v = (int8_t)(((int)G[noise_index(W, n)] + 1) >> 1);
+			for (int p = 0; p < npy; p++) arena_y[p * kFwArenaLuma + kArGuardLo + n] = v;
+		}
+		for (int n = tid; n < 44 * 38; n += 1024)
+		{
+			const int8_t v = (int8_t)(((int)G[noise_index(W + kFwStreamWords, n)] + 1) >> 1);
+			for (int p = 0; p < npc; p++) arena_c[p * kFwArenaChroma + kArGuardLo + n] = v;
+		}
+		__syncthreads();
+		// wavefronts 0..7: the luma patterns, 8..15: the chroma patterns (the index is made wave-uniform: the taps are scalar operands)
+		const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+		const bool chroma = wave >= kSlots;
+		const int p = wave & (kSlots - 1);
+		if (p < (chroma ? npc : npy))
+			ar_rows<2, 2>((chroma ? arena_c + p * kFwArenaChroma : arena_y + p * kFwArenaLuma) + kArGuardLo, jb.pat[wave], chroma ? 44 : 82,
+			              chroma ? 38 : 73, jb.ar_scale, tid & 63);
+		__syncthreads();
+	}
+
+	// ---- the model: record, zero fill, then every byte that is not zero
+	const bool pk16 = depth8 && kPk16;
+	const ImageLayout L = image_layout(csubx, csuby, one_y, one_c, depth8 != 0);
+	uint8_t* const img = jb.dst + kModelRecordBytes;
+	if (tid < kModelRecordBytes / 4) ((uint32_t*)jb.dst)[tid] = ((const uint32_t*)&jb.rec)[tid];
+	for (int o = tid; o < L.bytes / 16; o += 1024) ((uint4*)img)[o] = make_uint4(0u, 0u, 0u, 0u);
+	__threadfence();     // (the zeros have arrived before another wavefront stores to the same bytes)
+	__syncthreads();
+
+	// LUTs: build_tables' entries -- the selector of the pattern LUT's slot (an unused entry can name a slot the list does not hold) and the pre-shifted scale
+	if (tid < 3 * 256)
+	{
+		const int c = tid >> 8, i = tid & 255;
+		const bool one = c ? one_c : one_y;
+		uint32_t* lut = (uint32_t*)(img + (c == 0 ? L.y_off : c == 1 ? L.c_off[0] + L.c_lut[0] : L.c_off[1] + L.c_lut[1]));     // (no indexed member: no scratch)
+		if (pk16 && one)
+		{
+			if (i < 64) lut[i] = ((const uint32_t*)jb.slut[c])[i];     // the scale bytes themselves
+		}
+		else
+		{
+			const uint32_t sl = jb.plut[c][i] >> 4;
+			const uint32_t sel = sl < (uint32_t)kSlots ? sl : 0x0cu;
+			const int sc = (int)jb.slut[c][i] << (16 - jb.scale_shift);
+			lut[i] = (sel << 24) | ((uint32_t)sc & 0xffffffu);
+			if (!one) lut[256 + i] = (sel << 24) | ((uint32_t)(-sc) & 0xffffffu);
+		}
+	}
+
+	auto luma = [&](int s, int r, int x) { return (int)ypat[s * ysl + r * yp + x]; };
+	// chroma slot s as the bank copy leaves it (vfgs_hw.c:320-325; at 4:2:0 pitch = length = 32 and the tail is never reached)
+	const int cpitch = 64 / csuby;
+	auto chroma = [&](int s, int r, int x) {
+		const int i = cpitch * r + x;
+		if (i < 1024) return (int)cpat[s * csl + (i >> 5) * cp + (i & 31)];
+		return npy > 0 ? luma(npy - 1, i >> 6, i & 63) : 0;
+	};
+	// general form: the eight slot bytes of a sample in one store, slots the list does not hold zero
+	uint8_t* const ybank = img + L.y_off + L.y_bank;
+	if (!one_y)
+		for (int o = tid; o < 64 * 64; o += 1024)
+		{
+			const int r = o >> 6, x = o & 63;
+			uint32_t w[2] = {0u, 0u};
+#pragma unroll
+			for (int s = 0; s < kSlots; s++)
+				if (s < npy) w[s >> 2] |= (uint32_t)(uint8_t)luma(s, r, x) << (8 * (s & 3));
+			*(uint2*)(ybank + r * L.y_rs + x * kSlots) = make_uint2(w[0], w[1]);
+		}
+	else if (slot_y < npy)
+		sei_write_one(ybank, L.y_rs, L.y_neg, 64, 64, pk16, tid, [&](int r, int x) { return luma(slot_y, r, x); });
+	if (!one_c)
+		for (int o = tid; o < L.ch * L.cw; o += 1024)
+		{
+			const int r = o / L.cw, x = o % L.cw;
+			uint32_t w[2] = {0u, 0u};
+#pragma unroll
+			for (int s = 0; s < kSlots; s++)
+				if (s < npc) w[s >> 2] |= (uint32_t)(uint8_t)chroma(s, r, x) << (8 * (s & 3));
+#pragma unroll
+			for (int c = 0; c < 2; c++)     // (the general form holds the chroma bank once per component's sub-image)
+				*(uint2*)(img + L.c_off[c] + L.c_bank + r * L.c_rs + x * kSlots) = make_uint2(w[0], w[1]);
+		}
+	else
+#pragma unroll
+		for (int c = 0; c < 2; c++)     // Cb's and Cr's sub-image: each its own slot
+		{
+			const int s = c ? slot_cr : slot_cb;
+			if (s < npc)
+				sei_write_one(img + L.c_off[c] + L.c_bank, L.c_rs, L.c_neg, L.ch, L.cw, pk16, tid, [&](int r, int x) { return chroma(s, r, x); });
+		}
+}
+
+// ---------------------------------------------------------------------------------------
 // Copy device-generated slots into a device image (image_layout of vfgs_layout.h) that the host
 // has just uploaded with the host-set slots and the LUTs.  one_*: that plane type is stored in the
 // one-pattern form, holding slot slot_y / slot_cb / slot_cr only (8 = the all-zero pattern: nothing to copy).
@@ -532,6 +796,13 @@ hipError_t launch_fw_models(const FwConstants* k, const FwModelJob* jobs, int n,
 {
 	if (n <= 0 || n > kFwModelChunk) return hipErrorInvalidValue;
 	hipLaunchKernelGGL(fw_models_kernel, dim3(n), dim3(256), 0, stream, k, jobs, csubx, csuby, depth8);
+	return hipGetLastError();
+}
+
+hipError_t launch_fw_sei_build(const FwConstants* k, const FwSeiJob* jobs, int n, int csubx, int csuby, int depth8, hipStream_t stream)
+{
+	if (n <= 0 || n > kFwModelChunk) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(fw_sei_build_kernel, dim3(n), dim3(1024), 0, stream, k, jobs, csubx, csuby, depth8);
 	return hipGetLastError();
 }
 

@@ -1446,15 +1446,16 @@ void load_seed(State& s, uint32_t seed)
 // A released model's buffers go to a short queue with the events of those streams: they are handed to a later capture, or freed, only
 // after every launch queued before the release is done.
 //
-// Models built from parameter sets (vfgs_hip_models_from_afgs1 -> build_models) are written by ONE kernel per chunk of kFwModelChunk and
-// share one device allocation, the chunk's SLAB: the job table the kernel reads, then every model's record + image at a 16-byte aligned
-// offset.  The slab has the one SlotGuard of its models (one upload event per chunk, the streams that read any of them) and counts the
+// Models built from parameter sets (vfgs_hip_models_from_afgs1 -> build_models, vfgs_hip_models_from_sei -> build_models_sei) are written by
+// ONE kernel per chunk of kFwModelChunk and share one device allocation, the chunk's SLAB: the job table the kernel reads (its size is the
+// job type's: a slab serves a build only if its device bytes and its pinned staging bytes both suffice), then every model's record + image
+// at a 16-byte aligned offset.  The slab has the one SlotGuard of its models (one upload event per chunk, the streams that read any of them) and counts the
 // models not yet released; with the last release it is left like a captured model's buffers and waits in a short queue for the next
 // build, which takes it once its readers are done -- no allocation and no hipFree (which synchronises the device) in the steady state.
 struct ModelSlab {
-	uint8_t* dev = nullptr;               // [kFwModelChunk] FwModelJob, then the models
-	vfgs::FwModelJob* stage = nullptr;    // pinned source of the job table's copy
-	size_t cap = 0;
+	uint8_t* dev = nullptr;               // [kFwModelChunk] jobs (FwModelJob or FwSeiJob), then the models
+	uint8_t* stage = nullptr;             // pinned source of the job table's copy
+	size_t cap = 0, stage_cap = 0;        // bytes of dev, of stage
 	unsigned live = 0;                    // models of the slab that are not released yet
 	SlotGuard guard;
 };
@@ -2729,28 +2730,38 @@ namespace vfgs {
 // for the other host files of the library (vfgs_cfg_host.cpp): record an error like fail()
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 
-// Models from parameter sets (vfgs_model_build.h): the side of vfgs_hip_models_from_afgs1 that knows the programmed depth and format, the
-// slabs and the handles.  The programmed state is only READ here: no pending pattern request is flushed, nothing is generated into the
-// pattern banks, and the table ring, tables_dirty, the seeds and the mix are not looked at.
-int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model** out, void* stream_, FwModelsLauncher launch)
+// Models from parameter sets (vfgs_model_build.h): the side of vfgs_hip_models_from_afgs1 and vfgs_hip_models_from_sei that knows the
+// programmed depth and format, the slabs and the handles.  The programmed state is only READ here: no pending pattern request is flushed,
+// nothing is generated into the pattern banks, and the table ring, tables_dirty, the seeds and the mix are not looked at.
+//
+// One body for both job types (FwModelJob, FwSeiJob: dst, rec, one_y, one_c and scale_shift are theirs in common).  What differs comes as
+// two callbacks: check(s, job, i) refuses a job for the programmed state (0 or the code of fail()); form(s, job) stores the shift, chooses
+// the form of the image, fills the record, and returns whether the model clips to the legal range.
+namespace {
+ModelRecord model_record(const State& s, int ymin, int ymax, int cmin, int cmax, int stored_shift)
+{
+	ModelRecord r{};
+	r.lo2[0] = (uint32_t)(ymin << s.bs) * 0x10001u; r.hi2[0] = (uint32_t)(ymax << s.bs) * 0x10001u;
+	r.lo2[1] = (uint32_t)(cmin << s.bs) * 0x10001u; r.hi2[1] = (uint32_t)(cmax << s.bs) * 0x10001u;
+	r.pk_shift = stored_shift;
+	return r;
+}
+
+template <class Job, class Launcher, class Check, class Form>
+int build_models_of(const char* who, Job* jobs, unsigned n, vfgs_hip_model** out, void* stream_, Launcher launch, Check check, Form form)
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	if (int e = ensure_init(-1)) return e;
 	State& s = g_states[0];
 	const bool d8 = s.bs == 0;
 	for (unsigned i = 0; i < n; i++)
-	{
-		// FwModelJob::scale_shift arrives as the argument of vfgs_set_scale_shift and leaves as what that setter stores (vfgs_hw.c:349)
-		const int stored = jobs[i].scale_shift + 6 - s.bs;
-		if (stored + s.bs < 8 || stored + s.bs > 13)   // vfgs_hw.c:170, as vfgs_hip_model_capture
-			return fail(9, "%s: parameter set %u: grain_scaling %d at depth %d: scale_shift out of range (vfgs_hw.c:170)", who, i, jobs[i].scale_shift + 6, 8 + s.bs);
-	}
+		if (int e = check(s, jobs[i], i)) return e;
 	if (int e = fw_prepare(s)) return e;
 	hipStream_t stream = pick_stream(stream_);
 	size_t largest = 0;      // a slab holds kFwModelChunk models of the largest image of this depth and format, whatever this chunk's forms are
 	for (int f = 0; f < 2; f++)      // (all one-pattern, all general: the mixed forms lie between)
 		largest = std::max(largest, (size_t)layout_of(s.csubx, s.csuby, !f, !f, d8).bytes);
-	const size_t table_bytes = sizeof(FwModelJob) * kFwModelChunk;
+	const size_t table_bytes = sizeof(Job) * kFwModelChunk;
 	const size_t slab_bytes = table_bytes + kFwModelChunk * ((kModelRecordBytes + largest + 15) & ~(size_t)15);
 	std::vector<vfgs_hip_model*> made;
 	uint64_t launches = 0;
@@ -2762,10 +2773,11 @@ int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model**
 	for (unsigned c0 = 0; c0 < n; c0 += kFwModelChunk)
 	{
 		const unsigned cn = std::min<unsigned>(kFwModelChunk, n - c0);
-		// the oldest idle slab that is large enough, once its readers are done (normally long ago), else a new one
+		// the oldest idle slab that is large enough -- device bytes AND the pinned job table, which the other job type sizes differently --,
+		// once its readers are done (normally long ago), else a new one
 		ModelSlab* sl = nullptr;
 		for (size_t i = 0; i < g_slabs_idle.size() && !sl; i++)
-			if (g_slabs_idle[i]->cap >= slab_bytes) { sl = g_slabs_idle[i]; g_slabs_idle.erase(g_slabs_idle.begin() + (long)i); }
+			if (g_slabs_idle[i]->cap >= slab_bytes && g_slabs_idle[i]->stage_cap >= table_bytes) { sl = g_slabs_idle[i]; g_slabs_idle.erase(g_slabs_idle.begin() + (long)i); }
 		hipError_t e = hipSuccess;
 		if (sl) e = sl->guard.wait_free();
 		else
@@ -2774,30 +2786,21 @@ int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model**
 			e = hipMalloc((void**)&sl->dev, slab_bytes);
 			if (e == hipSuccess) { g_build_stats[4]++; e = hipHostMalloc((void**)&sl->stage, table_bytes, hipHostMallocDefault); }
 			sl->cap = slab_bytes;
+			sl->stage_cap = table_bytes;
 		}
 		size_t off = table_bytes;
+		bool legal[kFwModelChunk] = {};
 		for (unsigned k = 0; k < cn && e == hipSuccess; k++)
 		{
-			FwModelJob& j = jobs[c0 + k];
-			const int arg_shift = j.scale_shift;
-			j.scale_shift = arg_shift + 6 - s.bs;
-			bool one_y = lut_fits16(s.bs, j.scale_shift, j.slut[0]), one_c = lut_fits16(s.bs, j.scale_shift, j.slut[1]) && lut_fits16(s.bs, j.scale_shift, j.slut[2]);
-#ifdef VFGS_NO_ONE_PATTERN      // (image_form)
-			one_y = one_c = false;
-#endif
-			j.one_y = one_y; j.one_c = one_c;
-			const int ymin = j.legal ? 16 : 0, ymax = j.legal ? 235 : 255, cmax = j.legal ? 240 : 255;     // vfgs_set_legal_range
-			j.rec = ModelRecord{};
-			j.rec.lo2[0] = (uint32_t)(ymin << s.bs) * 0x10001u; j.rec.hi2[0] = (uint32_t)(ymax << s.bs) * 0x10001u;
-			j.rec.lo2[1] = (uint32_t)(ymin << s.bs) * 0x10001u; j.rec.hi2[1] = (uint32_t)(cmax << s.bs) * 0x10001u;
-			j.rec.pk_shift = j.scale_shift;
+			Job& j = jobs[c0 + k];
+			legal[k] = form(s, j);
 			j.dst = sl->dev + off;
-			const size_t bytes = (size_t)kModelRecordBytes + (size_t)layout_of(s.csubx, s.csuby, one_y, one_c, d8).bytes;
+			const size_t bytes = (size_t)kModelRecordBytes + (size_t)layout_of(s.csubx, s.csuby, j.one_y != 0, j.one_c != 0, d8).bytes;
 			off += (bytes + 15) & ~(size_t)15;
-			sl->stage[k] = j;
+			memcpy(sl->stage + sizeof(Job) * k, &j, sizeof(Job));
 		}
-		if (e == hipSuccess) e = hipMemcpyAsync(sl->dev, sl->stage, sizeof(FwModelJob) * cn, hipMemcpyHostToDevice, stream);
-		if (e == hipSuccess) e = launch(s.fw_const, (const FwModelJob*)sl->dev, (int)cn, s.csubx, s.csuby, d8, stream);
+		if (e == hipSuccess) e = hipMemcpyAsync(sl->dev, sl->stage, sizeof(Job) * cn, hipMemcpyHostToDevice, stream);
+		if (e == hipSuccess) e = launch(s.fw_const, (const Job*)sl->dev, (int)cn, s.csubx, s.csuby, d8, stream);
 		if (e == hipSuccess) e = sl->guard.uploaded(stream);
 		if (e != hipSuccess)
 		{
@@ -2808,13 +2811,13 @@ int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model**
 		launches++;
 		for (unsigned k = 0; k < cn; k++)
 		{
-			const FwModelJob& j = jobs[c0 + k];
+			const Job& j = jobs[c0 + k];
 			vfgs_hip_model* m = new vfgs_hip_model;
 			m->dev = j.dst;
 			m->bs = s.bs; m->csubx = s.csubx; m->csuby = s.csuby;
 			m->one_y = j.one_y != 0; m->one_c = j.one_c != 0;
 			m->scale_shift = j.scale_shift;
-			m->legal = j.legal != 0;
+			m->legal = legal[k];
 			m->rec = j.rec;
 			m->bytes = (size_t)kModelRecordBytes + (size_t)layout_of(s.csubx, s.csuby, m->one_y, m->one_c, d8).bytes;
 			m->slab = sl;
@@ -2825,6 +2828,56 @@ int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model**
 	for (unsigned i = 0; i < n; i++) { g_models.push_back(made[i]); out[i] = made[i]; }
 	g_build_stats[0]++; g_build_stats[1] += n; g_build_stats[2] += launches; g_build_stats[3] += launches;
 	return 0;
+}
+}  // namespace
+
+int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model** out, void* stream, FwModelsLauncher launch)
+{
+	return build_models_of(who, jobs, n, out, stream, launch,
+		[&](const State& s, const FwModelJob& j, unsigned i) {
+			// FwModelJob::scale_shift arrives as the argument of vfgs_set_scale_shift and leaves as what that setter stores (vfgs_hw.c:349)
+			const int stored = j.scale_shift + 6 - s.bs;
+			if (stored + s.bs < 8 || stored + s.bs > 13)   // vfgs_hw.c:170, as vfgs_hip_model_capture
+				return fail(9, "%s: parameter set %u: grain_scaling %d at depth %d: scale_shift out of range (vfgs_hw.c:170)", who, i, j.scale_shift + 6, 8 + s.bs);
+			return 0;
+		},
+		[](const State& s, FwModelJob& j) {
+			j.scale_shift = j.scale_shift + 6 - s.bs;
+			bool one_y = lut_fits16(s.bs, j.scale_shift, j.slut[0]), one_c = lut_fits16(s.bs, j.scale_shift, j.slut[1]) && lut_fits16(s.bs, j.scale_shift, j.slut[2]);
+#ifdef VFGS_NO_ONE_PATTERN      // (image_form)
+			one_y = one_c = false;
+#endif
+			j.one_y = one_y; j.one_c = one_c;
+			const int ymin = j.legal ? 16 : 0, ymax = j.legal ? 235 : 255, cmax = j.legal ? 240 : 255;     // vfgs_set_legal_range
+			j.rec = model_record(s, ymin, ymax, ymin, cmax, j.scale_shift);
+			return j.legal != 0;
+		});
+}
+
+// An SEI message carries no range: the model takes the programmed one, as vfgs_init_sei + vfgs_hip_model_capture would.  The form is
+// image_form's for ordinary rows on the derived tables: a component is one-pattern iff its pattern LUT is uniform and its scale LUT fits
+// the packed 16-bit form (the patterns are generated, hence clipped to +-127 and negatable; a slot the list does not hold is the zero pattern).
+int build_models_sei(const char* who, FwSeiJob* jobs, unsigned n, vfgs_hip_model** out, void* stream, FwSeiLauncher launch)
+{
+	return build_models_of(who, jobs, n, out, stream, launch,
+		[&](const State& s, const FwSeiJob& j, unsigned i) {
+			const int stored = j.scale_shift + 6 - s.bs;
+			if (stored + s.bs < 8 || stored + s.bs > 13)   // vfgs_hw.c:170, as vfgs_hip_model_capture
+				return fail(9, "%s: message %u: log2_scale_factor %d with the %s model at depth %d: scale_shift out of range (vfgs_hw.c:170)", who, i,
+				            j.scale_shift + (j.kind ? 1 : 0), j.kind ? "auto-regressive" : "frequency-filtered", 8 + s.bs);
+			return 0;
+		},
+		[](const State& s, FwSeiJob& j) {
+			j.scale_shift = j.scale_shift + 6 - s.bs;
+			auto fits = [&](int c) { return lut_fits16(s.bs, j.scale_shift, j.slut[c]); };
+			bool one_y = j.slot[0] >= 0 && fits(0), one_c = j.slot[1] >= 0 && j.slot[2] >= 0 && fits(1) && fits(2);
+#ifdef VFGS_NO_ONE_PATTERN      // (image_form)
+			one_y = one_c = false;
+#endif
+			j.one_y = one_y; j.one_c = one_c;
+			j.rec = model_record(s, s.ymin, s.ymax, s.cmin, s.cmax, j.scale_shift);
+			return s.ymin != 0;
+		});
 }
 }
 

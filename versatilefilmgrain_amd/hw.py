@@ -129,6 +129,7 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_get_model_build_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_model_build_stats.restype = None
     lib.vfgs_hip_models_from_afgs1.argtypes = [vp, u, C.POINTER(vp), vp]
+    lib.vfgs_hip_models_from_sei.argtypes = [vp, u, C.POINTER(vp), vp]
     lib.vfgs_hip_add_grain_frame_list_models_dev.argtypes = [fp, fp, C.POINTER(vp), sp, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_sp_frame_list_models_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
@@ -411,6 +412,21 @@ class VfgsHip:
         arr = (fw.FgsAfgs1 * len(cfgs))(*cfgs)
         out = (C.c_void_p * len(cfgs))()
         self._ck(self.lib.vfgs_hip_models_from_afgs1(arr, len(cfgs), out, stream))
+        return list(out)
+
+    def models_from_sei(self, cfgs, stream=0):
+        """Models straight from FGC SEI messages (fw.FgsSei objects), one kernel launch per 32 of them, at the programmed depth, chroma format
+        and legal range: handles like model_capture's, each what `reset_state(); <depth, format, range>; fw.init_sei(cfg); model_capture()`
+        would give, byte for byte in every form, with the programmed state untouched.  A message carries no seed: the pictures' seeds are the
+        caller's, for the list call.  VfgsHipError 42: a message vfgs_init_sei would abort on or read past (the message names its index),
+        9: log2_scale_factor out of range; nothing is built then."""
+        from . import fw
+        cfgs = list(cfgs)
+        if not cfgs:
+            return []
+        arr = (fw.FgsSei * len(cfgs))(*cfgs)
+        out = (C.c_void_p * len(cfgs))()
+        self._ck(self.lib.vfgs_hip_models_from_sei(arr, len(cfgs), out, stream))
         return list(out)
 
     def model_image(self, m):
