@@ -379,6 +379,18 @@ int  vfgs_hip_model_capture(vfgs_hip_model** out, void* stream);
 void vfgs_hip_model_release(vfgs_hip_model* m);
 int  vfgs_hip_model_info(const vfgs_hip_model* m, int out[8]);
 
+/* A MODEL WITH A CHROMA MIX OF ITS OWN.  vfgs_hip_model_capture drops an active luma / chroma mix (vfgs_hip_set_chroma_mix): its models
+ * carry none.  vfgs_hip_model_capture_mix is that call plus the mix that is active NOW: the model carries it -- per component the values and
+ * the `active` flag of vfgs_hip_get_chroma_mix -- in its record, and the two list calls with a model per picture below honour it frame by
+ * frame.  With no mix active the result cannot be told apart from vfgs_hip_model_capture's.  With one active the call refuses with 38 what
+ * the processing calls refuse under that mix: depth 12, or a programmed model that needs a general-form pattern bank; the other refusals
+ * are capture's.  The programmed state, the mix included, is unchanged either way.  Models built from AFGS1 parameter sets get their mix
+ * from vfgs_hip_models_from_afgs1_mix (vfgs_hip_fw.h).
+ * vfgs_hip_model_chroma_mix: out[4] = { luma_mult, chroma_mult, offset, active } of component c (1 = Cb, 2 = Cr) as the model carries them, in
+ * the units of vfgs_hip_get_chroma_mix; all zero for a model without a mix.  41: a null or released handle; 37: c is neither 1 nor 2. */
+int  vfgs_hip_model_capture_mix(vfgs_hip_model** out, void* stream);
+int  vfgs_hip_model_chroma_mix(const vfgs_hip_model* m, int c, int out[4]);
+
 /* Read back what a model holds on the device: the 32-byte record (clip bounds, the packed form's shift) followed by the table image, *bytes
  * (may be NULL) = their size = out[7] of vfgs_hip_model_info.  Synchronises (it waits for the work that made the model, on whatever stream);
  * for tests and debugging, like vfgs_hip_get_pattern.  41: a null or released handle; 6: `cap` is smaller than the size (or `out` is NULL),
@@ -405,14 +417,23 @@ void vfgs_hip_get_model_build_stats(uint64_t out[8]);
  * a change of form inside the list starts a new launch, a change of anything else -- patterns, LUTs, scale shift, range -- does not.
  * vfgs_hip_last_launch_info(): listed = 1, kernel grain_ml_kernel<depth,csubx,csuby,oney,onec>, `launches` counts every run.  The frames'
  * model images travel in the kernel arguments like their plane pointers: no copy is queued in front of a launch on account of models.
+ * MODELS THAT CARRY A MIX (vfgs_hip_model_capture_mix, vfgs_hip_models_from_afgs1_mix): "the state models[f] was captured from" includes
+ * its mix, and the single-frame call of the loop honours it -- while the library's programmed mix stays what it was (none: see the
+ * refusals).  Whether a model carries a mix is part of what a run shares: a launch holds at most 32 consecutive frames whose models agree
+ * in (one_y, one_c, carries a mix); the VALUES of the mix may change from frame to frame inside it.  Such a run is served by
+ * grain_mix_kernel<depth,csubx,csuby,false,false>, each workgroup taking image, bounds, shift and mix from its frame's model; runs without
+ * a mix are grain_ml_kernel's as before.  The in-place rule is the programmed mix's: where a destination luma plane of the run shares
+ * bytes with a source luma plane, the run is TWO launches, chroma first, and `launches` counts both.
  * Inside an overlap region the call alternates over the two internal streams like every device-pointer call; it runs on the primary device.
  * Refused before anything changes (a refused call does not reseed): everything the list calls refuse, with their codes (18 a null list or
  * plane, planes that share bytes; 7; 5 / 6 / 8 / 17 geometry; 15) -- except that the scale shift that counts is each model's, checked at
  * capture, and that a null `seeds` selects the single seed sequence (no error 39) -- and, error 41 with a message that names the cause:
  * models == NULL, or a NULL or released entry; a model captured at another depth or chroma format than the programmed one; width > 8192
- * (rows walked in parts); an active chroma mix ("chroma mix" in the message).  An empty list is no call at all.
- * Out of scope, on purpose: the mix per model, the narrowed 8-bit destination, stripe / part forms, host-memory entry points, widths
- * above 8192, persistent luma workgroups (1080p general-form luma runs without them here).  Semi-planar surfaces have the call below. */
+ * (rows walked in parts); an active PROGRAMMED chroma mix ("chroma mix" in the message: a mix reaches this call in its models).  A model
+ * that carries a mix adds no refusal of its own: depth and form were checked where the mix was attached.  An empty list is no call at all.
+ * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination (with or without a mix),
+ * stripe / part forms, host-memory entry points, widths above 8192, persistent luma workgroups (1080p general-form luma runs
+ * without them here).  Semi-planar surfaces have the call below. */
 int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
                                              const vfgs_hip_model* const* models,     /* nframes entries */
                                              const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
@@ -427,20 +448,22 @@ int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, con
  *     for f in list order:
  *         program the state models[f] was captured from;
  *         if (seeds) vfgs_set_seed(seeds[f]);
- *         vfgs_hip_add_grain_sp_frame_list_dev(&src[f], &dst[f], NULL, 1, ...)      (no chroma mix active)
- * and the library's own programmed state is UNCHANGED by the call.
- * Launches: one per run of at most 32 consecutive frames whose models share (one_y, one_c); a change of form starts a new launch, a change
- * of anything else does not.  vfgs_hip_last_launch_info(): listed = 1, kernel grain_spml_kernel<depth,csuby,oney,onec>, `launches` counts
- * every run.  No copy is queued in front of a launch on account of models.  In place is ONE launch: there is no mix, so no luma hazard.
+ *         vfgs_hip_add_grain_sp_frame_list_dev(&src[f], &dst[f], NULL, 1, ...)      (under the mix models[f] carries, if it carries one)
+ * and the library's own programmed state, its mix included, is UNCHANGED by the call.
+ * Launches: one per run of at most 32 consecutive frames whose models share (one_y, one_c, carries a mix); a change of any of the three
+ * starts a new launch, a change of anything else -- the values of the mix included -- does not.  vfgs_hip_last_launch_info(): listed = 1,
+ * kernel grain_spml_kernel<depth,csuby,oney,onec>, for a run of models that carry a mix grain_sp_mix_kernel<depth,csuby>; `launches` counts
+ * every launch.  No copy is queued in front of a launch on account of models.  In place is ONE launch for a run without a mix (no luma
+ * hazard) and TWO, UV first, for a run with one, where a destination luma plane shares bytes with a source luma plane.
  * Inside an overlap region the call alternates over the two internal streams; it runs on the primary device.
  * Refused before anything changes (a refused call does not reseed): everything vfgs_hip_add_grain_sp_frame_list_dev refuses, with its
  * codes (18 a null list or plane, planes that share bytes -- a UV plane that overlaps another frame's Y included; 7; 5 / 6 / 8 geometry);
  * error 40 for csubx != 2, a bad sample_shift, width > 8192; the scale shift that counts is each model's, checked at capture; error 41 with
  * a message that names the cause: models == NULL, a NULL or released entry, a model captured at another depth or chroma format than the
- * programmed one, an active chroma mix ("chroma mix" in the message).  Where several apply: the list checks, then 40, then 41.  An empty
- * list is no call at all.
- * Out of scope, on purpose: the mix per model, the narrowed 8-bit destination, a planar source, stripe / part forms, host-memory entry
- * points, 4:4:4, widths above 8192. */
+ * programmed one, an active PROGRAMMED chroma mix ("chroma mix" in the message).  Where several apply: the list checks, then 40, then 41.
+ * An empty list is no call at all.
+ * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination, a planar source, stripe / part
+ * forms, host-memory entry points, 4:4:4, widths above 8192. */
 int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                                 const vfgs_hip_model* const* models,   /* nframes entries, host memory */
                                                 const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */

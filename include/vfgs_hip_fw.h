@@ -107,8 +107,8 @@ unsigned int vfgs_hip_afgs1_seed(const fgs_afgs1* cfg);
  * general form; the slots no LUT selects are zero there) and the reference firmware's quirks as vfgs_init_afgs1 restates them.
  * The PROGRAMMED STATE IS UNTOUCHED: host mirror, device pattern banks, pending pattern requests, table images, depth and format, the four
  * seed registers, the chroma mix and its switch are what they were.  The picture's seed stays the caller's business --
- * vfgs_hip_afgs1_seed(&cfgs[i]) goes into the list call's `seeds` -- and cb_mult and the other mix fields are ignored: a model carries
- * no mix, as with capture.
+ * vfgs_hip_afgs1_seed(&cfgs[i]) goes into the list call's `seeds` -- and cb_mult and the other mix fields are ignored by THIS call: its
+ * models carry no mix, as with vfgs_hip_model_capture.  vfgs_hip_models_from_afgs1_mix below attaches them.
  * One kernel serves up to 32 models (one workgroup each: the luma and the Cb recursion side by side, then the whole record + image
  * written from LDS), so a call queues ONE copy (the job table) and ONE launch per 32 models; the models of such a chunk share one device
  * allocation that returns to a small pool with the last release: no allocation and no free in the steady state of build / grain / release
@@ -125,6 +125,21 @@ unsigned int vfgs_hip_afgs1_seed(const fgs_afgs1* cfg);
 struct vfgs_hip_model;
 int vfgs_hip_models_from_afgs1(const fgs_afgs1* cfgs, unsigned n, struct vfgs_hip_model** out, void* stream);
 
+/* ... WITH THE CHROMA MIX OF EACH PARAMETER SET.  vfgs_hip_models_from_afgs1 in every respect -- refusals 41 / 42 / 9, one copy and one
+ * launch per 32 models, the slab pool and its counters, the programmed state untouched, the mix and its switch included -- and in addition
+ * out[i] CARRIES the mix vfgs_init_afgs1 programs with the switch of vfgs_hip_afgs1_chroma_mix on, whatever the switch says:
+ *   chroma_scaling_from_luma ? (64, 0, 0) : (cb_luma_mult - 128, cb_mult - 128, cb_offset - 256), and the same for Cr,
+ * both components active (vfgs_hip_set_chroma_mix's rule: a component that was set is).  out[i] is what
+ *     vfgs_hip_afgs1_chroma_mix(1); vfgs_init_afgs1(&cfgs[i]); vfgs_hip_model_capture_mix(&out[i], stream);
+ * gives (vfgs_hip.h), record and image byte for byte; vfgs_hip_model_chroma_mix reads the mix back, and the two list calls with a model per
+ * picture honour it frame by frame, 32 pictures per launch (grain_mix_kernel / grain_sp_mix_kernel).  The kernel that builds the models
+ * writes the mix with the record: no second kernel, no further copy.
+ * FURTHER REFUSALS, the message naming the index:
+ *   42  a mix field vfgs_hip_set_chroma_mix would refuse (37 there): cb_offset / cr_offset above 511
+ *   38  what the processing calls refuse under a mix: the programmed depth is 12; or, at 8 bit, a scaling function that does not fit the
+ *       packed 16-bit form, so that the image would fall back to the general form (the models of the mix are all-one-pattern) */
+int vfgs_hip_models_from_afgs1_mix(const fgs_afgs1* cfgs, unsigned n, struct vfgs_hip_model** out, void* stream);
+
 /* ... AND FROM FGC SEI MESSAGES.  A VVC / HEVC player that receives an FGC SEI with a picture (the reference CLI's `-c <poc>:<file>`) gets its
  * models the same way.  The call works at the programmed depth, chroma format AND legal range (vfgs_set_depth, vfgs_set_chroma_subsampling,
  * vfgs_set_legal_range: fgs_sei carries no range and vfgs_init_sei sets none); out[i] is a live model that no call taking models -- the two
@@ -137,8 +152,9 @@ int vfgs_hip_models_from_afgs1(const fgs_afgs1* cfgs, unsigned n, struct vfgs_hi
  * on different slots -- and both scale LUTs fit; a uniform slot the list does not hold (an absent component, the unused entry the
  * reference's pattern search can match) is the zero pattern.  The reference firmware's quirks are those vfgs_init_sei restates.
  * The PROGRAMMED STATE IS UNTOUCHED: host mirror, device pattern banks, pending pattern requests, table images, depth, format and range, the
- * four seed registers, the chroma mix and its switch are what they were.  A model carries no mix; an SEI carries no seed: the seed stays
- * the caller's (`seeds` of the list call, or the running sequence).
+ * four seed registers, the chroma mix and its switch are what they were.  A model from an SEI carries no mix (an SEI has none;
+ * vfgs_hip_models_from_afgs1_mix and vfgs_hip_model_capture_mix make models that do); an SEI carries no seed: the seed stays the caller's
+ * (`seeds` of the list call, or the running sequence).
  * One kernel serves up to 32 models (one workgroup each: every pattern of the message -- up to 8 luma and 8 chroma -- made in LDS, then the
  * whole record + image written from there), so a call queues ONE copy (the job table) and ONE launch per 32 models; the models of a chunk
  * share one device allocation from the pool of vfgs_hip_models_from_afgs1, and vfgs_hip_get_model_build_stats counts both calls in the same

@@ -1468,6 +1468,10 @@ struct vfgs_hip_model {
 	bool one_y = false, one_c = false;
 	int scale_shift = 0, legal = 0;
 	vfgs::ModelRecord rec{};
+	// the host's view of the record's mix words (mirror_mix): whether the model carries a mix -- which kernel family serves it -- and per
+	// component { luma_mult, chroma_mult, offset, active } in the units of vfgs_hip_get_chroma_mix
+	bool has_mix = false;
+	int mix[2][4] = {};
 	size_t cap = 0, bytes = 0;
 	SlotGuard guard;
 	ModelSlab* slab = nullptr;    // a built model: dev points into this slab, host is null, and the guard is the slab's
@@ -1475,10 +1479,23 @@ struct vfgs_hip_model {
 
 namespace {
 
-struct ModelRun {                 // what run_device needs to know about the models of ONE launch: their common form, and frame 0's record
-	bool one_y, one_c;
+struct ModelRun {                 // what run_device needs to know about the models of ONE launch: their common form, whether they carry a mix, and frame 0's record
+	bool one_y, one_c, mix;
 	vfgs::ModelRecord first;
 };
+
+// m->rec is final: what it says about the mix, on the handle
+void mirror_mix(vfgs_hip_model* m)
+{
+	m->has_mix = (m->rec.mix_flags & 1u) != 0;
+	for (int c = 0; c < 2; c++)
+	{
+		const uint32_t w = m->has_mix ? m->rec.mix[c] : 0u;
+		m->mix[c][0] = vfgs::model_mix_luma_mult(w); m->mix[c][1] = vfgs::model_mix_chroma_mult(w);
+		m->mix[c][2] = vfgs::model_mix_offset(w) >> m->bs;     // (stored << (depth - 8): exact)
+		m->mix[c][3] = vfgs::model_mix_active(w);
+	}
+}
 
 std::vector<vfgs_hip_model*> g_models;        // live models (a handle that is not in here is refused, or ignored by release)
 std::vector<vfgs_hip_model*> g_models_left;   // released, oldest first: buffers that queued launches may still read
@@ -1637,7 +1654,7 @@ int Launch::admit()
 	if (p2sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (mr && (!list || p2sp || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
-		return fail(19, "internal: a model per frame goes with listed whole frames, planar or semi-planar, of at most %d samples a row, without a chroma mix", vfgs::kTileBlocks * 16);
+		return fail(19, "internal: a model per frame goes with listed whole frames, planar or semi-planar, of at most %d samples a row, without a programmed chroma mix", vfgs::kTileBlocks * 16);
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) { nothing = true; return 0; }
 	if (!mr)
@@ -1674,7 +1691,9 @@ int Launch::admit()
 	else if (s.plut_bad_c < 0) image_form(s, wide, &form_one_y, &form_one_c);
 	// the mix has kernels for the all-one-pattern images (AFGS1) on the library's primary device; refused before any state moves
 	// (the semi-planar call refuses the same cases under its own code, 40: the two entries stay congruent on the planar picture)
-	mix = mix_active();
+	// (a model per frame: the run's models carry a mix of their own -- depth and form were checked where it was attached -- and the programmed
+	// one, refused above, is not looked at)
+	mix = mr ? mr->mix : mix_active();
 	if (mix && p2sp) return fail(19, "internal: a planar source with a semi-planar destination under a chroma mix");     // (refused with code 40 at the entry)
 	const int mix_code = sp ? 40 : 38;
 	const char* const mix_who = sp ? "semi-planar frames: " : "";
@@ -1903,8 +1922,11 @@ int Launch::launch()
 	                      p2sp ? (dg.out8 ? Family::p2sp8 : Family::p2sp)
 	                      : sp ? (mix ? Family::sp_mix : dg.out8 ? Family::sp8 : mr ? Family::spml : Family::sp)
 	                           : (mix ? Family::mix : mr ? Family::ml : Family::rw)};
-	if (mr && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
-	const vfgs::FamilyFields ff = vfgs::family_fields(key.family);
+	// (models that carry a mix: the kernels of the mix, which take image, bounds and mix from the frame's model where models_kernel is set)
+	const bool mix_models = mr && mix;
+	if (mr && !mix_models && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
+	if (mix_models && (key.out8 || key.wide)) return fail(19, "internal: models that carry a mix were admitted for a narrowed destination or rows walked in parts");
+	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models);
 	a.models_kernel = ff.models_kernel; a.mix_kernel = ff.mix_kernel; a.sp_kernel = ff.sp_kernel;
 	if (sp || p2sp) a.sp_shift2 = sample_shift * 0x10001u;
 	if (mix)
@@ -1912,7 +1934,7 @@ int Launch::launch()
 		// (semi-planar frames: grain_sp_mix_kernel, whose UV workgroups read the luma over their rows; the same two-launch rule)
 		if (!(img_one_y && img_one_c) || persist) return fail(19, "internal: the table image is not the form the chroma mix was admitted for");
 		a.mix_lw = (int)width;
-		for (int c = 0; c < 2; c++)
+		for (int c = 0; c < 2 && !mr; c++)     // (a model per frame: the mix is in each frame's record, these stay zero and unread)
 		{
 			a.mix[c][0] = g_mix[c][0]; a.mix[c][1] = g_mix[c][1];
 			a.mix[c][2] = g_mix[c][2] * (1 << s.bs);
@@ -2819,6 +2841,7 @@ int build_models_of(const char* who, Job* jobs, unsigned n, vfgs_hip_model** out
 			m->scale_shift = j.scale_shift;
 			m->legal = legal[k];
 			m->rec = j.rec;
+			mirror_mix(m);
 			m->bytes = (size_t)kModelRecordBytes + (size_t)layout_of(s.csubx, s.csuby, m->one_y, m->one_c, d8).bytes;
 			m->slab = sl;
 			sl->live++;
@@ -2839,6 +2862,16 @@ int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model**
 			const int stored = j.scale_shift + 6 - s.bs;
 			if (stored + s.bs < 8 || stored + s.bs > 13)   // vfgs_hw.c:170, as vfgs_hip_model_capture
 				return fail(9, "%s: parameter set %u: grain_scaling %d at depth %d: scale_shift out of range (vfgs_hw.c:170)", who, i, j.scale_shift + 6, 8 + s.bs);
+			// a model that carries a mix (vfgs_hip_models_from_afgs1_mix): what the processing calls refuse under a programmed mix is refused
+			// where the mix is attached -- the kernels of the mix exist for all-one-pattern images at 8 and 10 bit
+			if (j.mix_carried && s.bs == 4)
+				return fail(38, "%s: parameter set %u: a model with a chroma mix at depth 12: the kernels of the mix exist at 8 and 10 bit", who, i);
+			if (j.mix_carried && !(lut_fits16(s.bs, stored, j.slut[0]) && lut_fits16(s.bs, stored, j.slut[1]) && lut_fits16(s.bs, stored, j.slut[2])))
+				return fail(38, "%s: parameter set %u: a scaling function does not fit the packed 16-bit form, the image needs a general-form pattern bank: not supported with a chroma mix", who, i);
+#ifdef VFGS_NO_ONE_PATTERN      // (a developer's build in which every image takes the general form, below: refused here, not at the list call)
+			if (j.mix_carried)
+				return fail(38, "%s: parameter set %u: this build makes general-form images only (VFGS_NO_ONE_PATTERN): not supported with a chroma mix", who, i);
+#endif
 			return 0;
 		},
 		[](const State& s, FwModelJob& j) {
@@ -2850,6 +2883,12 @@ int build_models(const char* who, FwModelJob* jobs, unsigned n, vfgs_hip_model**
 			j.one_y = one_y; j.one_c = one_c;
 			const int ymin = j.legal ? 16 : 0, ymax = j.legal ? 235 : 255, cmax = j.legal ? 240 : 255;     // vfgs_set_legal_range
 			j.rec = model_record(s, ymin, ymax, ymin, cmax, j.scale_shift);
+			if (j.mix_carried)      // the record's mix words: the job's, with the offset in samples of the programmed depth (KernelArgs::mix)
+			{
+				j.rec.mix_flags = 1;
+				for (int c = 0; c < 2; c++)
+					j.rec.mix[c] = model_mix_word(model_mix_luma_mult(j.mix[c]), model_mix_chroma_mult(j.mix[c]), model_mix_offset(j.mix[c]) * (1 << s.bs), model_mix_active(j.mix[c]));
+			}
 			return j.legal != 0;
 		});
 }
@@ -3404,11 +3443,12 @@ static int launch_list(ListCall& l)
 	GrainCall& c = l.call;     // (the planes, the frame count and the list of each launch in turn)
 	for (unsigned f0 = 0, n = 0; f0 < l.nframes; f0 += n)
 	{
-		// one launch: kListFrames frames at most -- with a model per frame, a run of frames whose models share the form of their images
+		// one launch: kListFrames frames at most -- with a model per frame, a run of frames whose models share the form of their images and
+		// whether they carry a mix (which kernel family serves them; the values of the mix may differ from frame to frame)
 		n = std::min<unsigned>(vfgs::kListFrames, l.nframes - f0);
 		if (models)
 			for (unsigned k = 1; k < n; k++)
-				if (models[f0 + k]->one_y != models[f0]->one_y || models[f0 + k]->one_c != models[f0]->one_c) { n = k; break; }
+				if (models[f0 + k]->one_y != models[f0]->one_y || models[f0 + k]->one_c != models[f0]->one_c || models[f0 + k]->has_mix != models[f0]->has_mix) { n = k; break; }
 		vfgs::FrameTable ft{};
 		for (unsigned k = 0; k < n; k++)
 		{
@@ -3426,6 +3466,7 @@ static int launch_list(ListCall& l)
 				ft.model[k] = m->dev;
 			}
 			mr.one_y = models[f0]->one_y; mr.one_c = models[f0]->one_c;
+			mr.mix = models[f0]->has_mix;
 			mr.first = models[f0]->rec;
 			c.mr = &mr;
 		}
@@ -3570,10 +3611,11 @@ int vfgs_hip_add_grain_frame_list_seeded_copy8_dev(const vfgs_hip_frame_ptrs* sr
 // Models as objects (vfgs_hip.h).  Capture builds the image upload_tables would build for ordinary rows -- same form, same bytes, device-generated
 // slots patched in on the device -- into a buffer the model owns, with the record of per-launch values in front, and leaves the programmed
 // state, its image ring and tables_dirty alone.
-int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream_)
+// with_mix (vfgs_hip_model_capture_mix): the model also carries the mix that is active now -- none: the model of vfgs_hip_model_capture, byte for
+// byte -- and what the processing calls refuse under that mix (Launch::admit, code 38) is refused here, before anything moves.
+static int capture_model(const char* who, vfgs_hip_model** out, void* stream_, const bool with_mix)
 {
-	std::lock_guard<std::mutex> g(g_mu);
-	if (!out) return fail(41, "vfgs_hip_model_capture: null result pointer");
+	if (!out) return fail(41, "%s: null result pointer", who);
 	*out = nullptr;
 	if (int e = ensure_init(-1)) return e;
 	State& s = g_states[0];
@@ -3584,6 +3626,11 @@ int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream_)
 	const int slot[3] = {s.plut_slot[0], s.plut_slot[1], s.plut_slot[2]};
 	bool one_y, one_c;
 	image_form(s, false, &one_y, &one_c);
+	const bool carry = with_mix && mix_active();
+	if (carry && s.bs == 4)
+		return fail(38, "%s: a chroma mix is active and the depth is 12: the kernels of the mix exist at 8 and 10 bit", who);
+	if (carry && !(one_y && one_c))
+		return fail(38, "%s: a chroma mix is active and the programmed model needs a general-form pattern bank: not supported", who);
 	const vfgs::ImageLayout L = vfgs::layout_of(s.csubx, s.csuby, one_y, one_c, s.bs == 0);
 	const size_t bytes = (size_t)vfgs::kModelRecordBytes + (size_t)L.bytes;
 	if (int e = fw_flush(s, stream)) return e;
@@ -3600,7 +3647,7 @@ int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream_)
 		m = new vfgs_hip_model;
 		hipError_t e = hipMalloc((void**)&m->dev, bytes);
 		if (e == hipSuccess) e = hipHostMalloc((void**)&m->host, bytes, hipHostMallocDefault);
-		if (e != hipSuccess) { (void)hipGetLastError(); model_destroy(m); return fail((int)e, "vfgs_hip_model_capture: %zu bytes -> %s", bytes, hipGetErrorString(e)); }
+		if (e != hipSuccess) { (void)hipGetLastError(); model_destroy(m); return fail((int)e, "%s: %zu bytes -> %s", who, bytes, hipGetErrorString(e)); }
 		m->cap = bytes;
 	}
 	m->bytes = bytes;
@@ -3612,6 +3659,12 @@ int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream_)
 	m->rec.lo2[0] = (uint32_t)(s.ymin << s.bs) * 0x10001u; m->rec.hi2[0] = (uint32_t)(s.ymax << s.bs) * 0x10001u;
 	m->rec.lo2[1] = (uint32_t)(s.cmin << s.bs) * 0x10001u; m->rec.hi2[1] = (uint32_t)(s.cmax << s.bs) * 0x10001u;
 	m->rec.pk_shift = s.scale_shift;
+	if (carry)      // the active mix in the units of KernelArgs::mix (Launch::launch)
+	{
+		m->rec.mix_flags = 1;
+		for (int c = 0; c < 2; c++) m->rec.mix[c] = vfgs::model_mix_word(g_mix[c][0], g_mix[c][1], g_mix[c][2] * (1 << s.bs), g_mix[c][3]);
+	}
+	mirror_mix(m);
 	memcpy(m->host, &m->rec, sizeof m->rec);
 	build_tables(s, m->host + vfgs::kModelRecordBytes, L, one_y, one_c, slot);
 	hipError_t e = hipMemcpyAsync(m->dev, m->host, bytes, hipMemcpyHostToDevice, stream);
@@ -3629,10 +3682,31 @@ int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream_)
 	{
 		(void)hipStreamSynchronize(stream);     // (whatever was queued on the buffers is done before they go)
 		model_destroy(m);
-		return fwe ? fwe : fail((int)e, "vfgs_hip_model_capture: %s", hipGetErrorString(e));
+		return fwe ? fwe : fail((int)e, "%s: %s", who, hipGetErrorString(e));
 	}
 	g_models.push_back(m);
 	*out = m;
+	return 0;
+}
+
+int vfgs_hip_model_capture(vfgs_hip_model** out, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return capture_model("vfgs_hip_model_capture", out, stream, false);
+}
+
+int vfgs_hip_model_capture_mix(vfgs_hip_model** out, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return capture_model("vfgs_hip_model_capture_mix", out, stream, true);
+}
+
+int vfgs_hip_model_chroma_mix(const vfgs_hip_model* m, int c, int out[4])
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	if (!model_live(m)) return fail(41, "vfgs_hip_model_chroma_mix: %s", m ? "the model was released" : "null model");
+	if (c < 1 || c > 2 || !out) return fail(37, "vfgs_hip_model_chroma_mix: component %d (1 = Cb, 2 = Cr)", c);
+	for (int i = 0; i < 4; i++) out[i] = m->mix[c - 1][i];
 	return 0;
 }
 

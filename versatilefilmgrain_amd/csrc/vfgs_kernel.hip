@@ -689,7 +689,11 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     workgroup's FRAME -- FrameTable::model[f] points at a ModelRecord with the image behind it -- fetched with scalar loads (the pointer from
 //     the kernel arguments, the record through it) in front of the image loads; everything they feed stays wave-uniform.  Without the flag
 //     the values are the launch's, from KernelArgs, and nothing of this exists.
-template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0, bool MODELS = false>
+//     MODELS = 2 (both plane types of grain_mix_kernel without OUT8 and WIDE, the luma planes of grain_sp_mix_kernel): decided at RUN time by
+//     KernelArgs::models_kernel, a wave-uniform branch around the scalar loads -- the same kernel serves the programmed mix (the launch's
+//     values) and listed frames whose models carry a mix of their own (the frame's values; MIX: the mix words of its record too, not
+//     KernelArgs::mix).  A value of its own so that the instantiations every other kernel uses stay what they were.
+template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0, int MODELS = 0>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
 {
@@ -717,7 +721,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
-	static_assert(!MODELS || (!OUT8 && !WIDE && !PERSIST && !MIX && SP != 2), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup");
+	static_assert(!MODELS || (!OUT8 && !WIDE && !PERSIST && (!MIX || MODELS == 2) && SP != 2), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup; under the mix: decided at run time");
 	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
@@ -761,17 +765,24 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	constexpr int NIT = (IMG_BYTES + STEP - 1) / STEP;
 	u32x4 tmp[NIT];
 	// MODELS: my frame's model -- its record (constant address space: scalar loads) and the image behind it
-	const uint8_t* mtables = nullptr;
-	uint32_t mlo2 = 0, mhi2 = 0;
-	int mpk_shift = 0;
-	if constexpr (MODELS)
+	// (MODELS == 2: where the launch names no models these stay the launch's own values)
+	const uint8_t* mtables = MODELS == 2 ? a.tables : nullptr;
+	uint32_t mlo2 = MODELS == 2 ? a.lo2[pt] : 0, mhi2 = MODELS == 2 ? a.hi2[pt] : 0;
+	int mpk_shift = MODELS == 2 ? a.pk_shift : 0;
+	uint32_t mmix = 0;                    // MIX: my component's mix word of the record (model_mix_word)
+	const bool per_model = MODELS == 2 ? a.models_kernel != 0 : MODELS != 0;
+	if constexpr (MODELS != 0)
 	{
-		typedef const uint32_t __attribute__((address_space(4)))* crec_t;
-		const uint8_t* const mp = ft.model[f];
-		const crec_t rec = (crec_t)(uintptr_t)mp;
-		mlo2 = rec[pt]; mhi2 = rec[2 + pt];
-		mpk_shift = (int)rec[4];
-		mtables = mp + kModelRecordBytes;
+		if (per_model)
+		{
+			typedef const uint32_t __attribute__((address_space(4)))* crec_t;
+			const uint8_t* const mp = ft.model[f];
+			const crec_t rec = (crec_t)(uintptr_t)mp;
+			mlo2 = rec[pt]; mhi2 = rec[2 + pt];
+			mpk_shift = (int)rec[4];
+			if constexpr (MIX) mmix = rec[comp == 2 ? 7 : 6];
+			mtables = mp + kModelRecordBytes;
+		}
 	}
 	if (!PERSIST || first_task)
 	{
@@ -942,8 +953,11 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	uint32_t carry[4] = {0, 0, 0, 0};      // in lane 0: the last K dwords of lane 63 of the previous position of the row
 	uint32_t mcarry[4] = {0, 0, 0, 0};     // MIX: the same for the index dwords
 	const int mixc = comp == 2 ? 1 : 0;
-	const int mix_lm = MIX ? a.mix[mixc][0] : 0, mix_cm = MIX ? a.mix[mixc][1] : 0, mix_off = MIX ? a.mix[mixc][2] : 0;
-	const bool mix_on = MIX && a.mix[mixc][3] != 0;      // (a component without a mix of its own keeps the sample as its index)
+	// (a model per frame: the four values out of the frame's record, scalar bit-field extracts; KernelArgs::mix is not read)
+	const bool rmix = MIX && MODELS == 2 && per_model;
+	const int mix_lm = MIX ? (rmix ? model_mix_luma_mult(mmix) : a.mix[mixc][0]) : 0, mix_cm = MIX ? (rmix ? model_mix_chroma_mult(mmix) : a.mix[mixc][1]) : 0;
+	const int mix_off = MIX ? (rmix ? model_mix_offset(mmix) : a.mix[mixc][2]) : 0;
+	const bool mix_on = MIX && (rmix ? model_mix_active(mmix) != 0 : a.mix[mixc][3] != 0);      // (a component without a mix of its own keeps the sample as its index)
 	uint32_t outp[DW] = {};                // the previous position's units: dwords KD.. of its lanes (the first DW - KD dwords of a unit)
 	uint32_t tp[KD > 0 ? KD : 1] = {};     // ... and the first KD dwords its lanes computed: they belong one lane down
 	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);     // where the previous GROUP's last position goes
@@ -1316,10 +1330,14 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
 	int r = (int)(blockIdx.x >> a.lfronts);
 	if (f >= a.nframes) return;
+	// A model per frame (KernelArgs::models_kernel beside mix_kernel: listed frames whose models carry a mix): both walks take the
+	// image, the bounds, the shift and the mix from the frame's model, decided at run time (run_plane_rw MODELS = 2).  Not for the narrowed
+	// destination and not for rows walked in parts, which models do not have: those kernels are what they were.
+	constexpr int PM = (!OUT8 && !WIDE) ? 2 : 0;
 	if (r < a.pd[0].wgs)
 	{
 		if (a.mix_planes & 1) return;
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, true, L.y_neg, 0, OUT8, WIDE, false>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, true, L.y_neg, 0, OUT8, WIDE, false, false, 0, PM>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	}
 	else
 	{
@@ -1332,7 +1350,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 		int comp;
 		if (r < 2 * full) { comp = 1 + ((r >> 3) & 1); r = ((r >> 4) << 3) | (r & 7); }
 		else { r -= 2 * full; comp = 1 + (r >= n - full); r = full + (comp == 2 ? r - (n - full) : r); }
-		run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, true, L.c_neg, 0, OUT8, WIDE, false, true>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+		run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, true, L.c_neg, 0, OUT8, WIDE, false, true, 0, PM>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
 	}
 }
 
@@ -1367,7 +1385,9 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // MODELS (UV workgroups of grain_spml_kernel: a model per frame): both components' tables, the chroma clip bounds and the packed
 // form's shift are those of the workgroup's FRAME, as in run_plane_rw MODELS -- FrameTable::model[f] from the kernel arguments, the ModelRecord
 // through it with scalar loads, in front of the table loads; everything they feed stays wave-uniform.  Without the flag nothing of this exists.
-template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, bool MODELS = false>
+// MODELS = 2 (UV workgroups of grain_sp_mix_kernel): decided at run time by KernelArgs::models_kernel, as in run_plane_rw -- the frame's model
+// then also supplies both components' mix (the two mix words of its record), and KernelArgs::mix is not read.
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, int MODELS = 0>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
@@ -1386,7 +1406,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of them belong to the lane before its own
 	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0 && !MIX), "the narrowed destination exists for 16-bit containers, without the mix");
 	static_assert(!PLANAR || !MIX, "a planar source has no mix form");
-	static_assert(!MODELS || (!MIX && !OUT8 && !PLANAR), "a model per frame: the plain UV walk");
+	static_assert(!MODELS || (MIX == (MODELS == 2) && !OUT8 && !PLANAR), "a model per frame: the plain UV walk; under the mix: decided at run time");
 	constexpr bool DGEO = OUT8 || PLANAR;                // the destination has a geometry of its own
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
@@ -1422,17 +1442,24 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int NIT = (IMG + STEP - 1) / STEP;
 	u32x4 tmp[NIT];
 	// MODELS: my frame's model -- its record (constant address space: scalar loads) and the image behind it
-	const uint8_t* mtables = nullptr;
-	uint32_t mlo2 = 0, mhi2 = 0;
-	int mpk_shift = 0;
-	if constexpr (MODELS)
+	// (MODELS == 2: where the launch names no models these stay the launch's own values)
+	const uint8_t* mtables = MODELS == 2 ? a.tables : nullptr;
+	uint32_t mlo2 = MODELS == 2 ? a.lo2[1] : 0, mhi2 = MODELS == 2 ? a.hi2[1] : 0;
+	int mpk_shift = MODELS == 2 ? a.pk_shift : 0;
+	uint32_t mmix[2] = {0, 0};            // MIX: Cb's and Cr's mix word of the record (model_mix_word)
+	const bool per_model = MODELS == 2 ? a.models_kernel != 0 : MODELS != 0;
+	if constexpr (MODELS != 0)
 	{
-		typedef const uint32_t __attribute__((address_space(4)))* crec_t;
-		const uint8_t* const mp = ft.model[f];
-		const crec_t rec = (crec_t)(uintptr_t)mp;
-		mlo2 = rec[1]; mhi2 = rec[3];
-		mpk_shift = (int)rec[4];
-		mtables = mp + kModelRecordBytes;
+		if (per_model)
+		{
+			typedef const uint32_t __attribute__((address_space(4)))* crec_t;
+			const uint8_t* const mp = ft.model[f];
+			const crec_t rec = (crec_t)(uintptr_t)mp;
+			mlo2 = rec[1]; mhi2 = rec[3];
+			mpk_shift = (int)rec[4];
+			if constexpr (MIX) { mmix[0] = rec[6]; mmix[1] = rec[7]; }
+			mtables = mp + kModelRecordBytes;
+		}
 	}
 	{
 		// (the device image holds [LUT Cb][bank][LUT Cr][bank]: one-pattern form -- both sub-images as they are; general form -- LDS offset o
@@ -1564,9 +1591,15 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	// (each value a scalar register of its own: the eight come out of ONE scalar load, and kept as its 8-register tuple they would be spilled as
 	// one -- to a stack slot, the only scratch of the kernel; grain_sp_mix_kernel below says what guards this and what to do when it stops working)
 	auto own = [](int v) { if constexpr (MIX) asm("" : "+s"(v)); return v; };
-	const int mix_lm[2] = {MIX ? own(a.mix[0][0]) : 0, MIX ? own(a.mix[1][0]) : 0}, mix_cm[2] = {MIX ? own(a.mix[0][1]) : 0, MIX ? own(a.mix[1][1]) : 0};
-	const int mix_off[2] = {MIX ? own(a.mix[0][2]) : 0, MIX ? own(a.mix[1][2]) : 0};
-	const bool mix_on[2] = {MIX && own(a.mix[0][3]) != 0, MIX && own(a.mix[1][3]) != 0};
+	// (a model per frame: the values out of the frame's record, scalar bit-field extracts; KernelArgs::mix is not read)
+	const bool rmix = MIX && MODELS == 2 && per_model;
+	auto pick = [&](const int c, const int i) {
+		if (!rmix) return a.mix[c][i];
+		return i == 0 ? model_mix_luma_mult(mmix[c]) : (i == 1 ? model_mix_chroma_mult(mmix[c]) : (i == 2 ? model_mix_offset(mmix[c]) : model_mix_active(mmix[c])));
+	};
+	const int mix_lm[2] = {MIX ? own(pick(0, 0)) : 0, MIX ? own(pick(1, 0)) : 0}, mix_cm[2] = {MIX ? own(pick(0, 1)) : 0, MIX ? own(pick(1, 1)) : 0};
+	const int mix_off[2] = {MIX ? own(pick(0, 2)) : 0, MIX ? own(pick(1, 2)) : 0};
+	const bool mix_on[2] = {MIX && own(pick(0, 3)) != 0, MIX && own(pick(1, 3)) != 0};
 	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);
 	// the previous position is complete: interleave its two planar units, shift them up, store 32 bytes
 	auto store_prev = [&](const __amdgpu_buffer_rsrc_t rs, const uint32_t off) {
@@ -1924,10 +1957,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpMixWgPerCU) void grain_sp_mix_
 	own(b.cur_bit0); own(b.up_bit0); own(b.frame_bit_step); own(b.y0); own(b.nblk); own(b.nbrows); own(b.nframes); own(b.listed);
 	// (the same for the four of the luma geometry that arrive with pd[0].wgs above)
 	own(b.pd[0].nrows); own(b.pd[0].wgs); own(b.pd[0].rw_segs); own(b.pd[0].rw_rpw);
+	// (a model per frame -- KernelArgs::models_kernel beside mix_kernel -- is decided at run time in both walks, as in grain_mix_kernel: MODELS = 2)
 	if (luma)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, true, L.y_neg, 0, false, false, false, false, true>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, true, L.y_neg, 0, false, false, false, false, true, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
-		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, true, L.c_neg, true>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, true, L.c_neg, true, false, false, 2>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1938,7 +1972,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpMixWgPerCU) void grain_sp_mix_
 static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const KernelKey& k)
 {
 	const Family f = k.family;
-	const FamilyFields ff = family_fields(f);
+	// (the two families of the mix serve a model per frame too -- models that carry a mix -- with the kernels that decide it at run time: neither
+	// the narrowed destination nor rows walked in parts)
+	const bool mix_models = (f == Family::mix || f == Family::sp_mix) && a.models_kernel != 0;
+	if (mix_models && (k.out8 || k.wide)) return false;
+	const FamilyFields ff = family_fields(f, mix_models);
 	if (a.models_kernel != ff.models_kernel || a.mix_kernel != ff.mix_kernel || a.sp_kernel != ff.sp_kernel) return false;
 	if (k.wide != (a.nblk > kTileBlocks)) return false;
 	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return false;

@@ -275,13 +275,30 @@ struct FrameTable {
 // What a captured model (vfgs_hip_model_capture) keeps in front of its table image: the values that are one per launch in KernelArgs
 // for every other call -- lo2 / hi2 per plane type and pk_shift, exactly as KernelArgs holds them.  A workgroup of grain_ml_kernel reads
 // its frame's record with scalar loads before it issues the loads of the image.  32 bytes: the image behind it stays 16-byte aligned.
+//
+// A model may carry a luma / chroma mix of its own (vfgs_hip_models_from_afgs1_mix, vfgs_hip_model_capture_mix): mix_flags bit 0, and per
+// chroma component one word with the four values of KernelArgs::mix in its units (model_mix_word).  All three words zero = a model without
+// a mix, which is what every other way to a model writes: the record of before, byte for byte.  The kernels of the mix read the words where
+// a launch names a model per frame (KernelArgs::models_kernel with mix_kernel); no other kernel looks at them.
 struct ModelRecord {
 	uint32_t lo2[2], hi2[2];
 	int32_t pk_shift;
-	uint32_t reserved[3];
+	uint32_t mix_flags;           // bit 0: the model carries a mix
+	uint32_t mix[2];              // Cb, Cr: model_mix_word
 };
 constexpr int kModelRecordBytes = 32;
 static_assert(sizeof(ModelRecord) == kModelRecordBytes, "the table image begins 32 bytes behind the record");
+
+// One component's mix in a record: bits 7:0 luma_mult, 15:8 chroma_mult (both -128..127), 27:16 offset << (depth - 8) (-256..255 at 8 bit, four
+// times that at 10: twelve signed bits), bit 31 active.  Each field comes out with one scalar bit-field extract.
+constexpr uint32_t model_mix_word(const int luma_mult, const int chroma_mult, const int offset_scaled, const int active)
+{
+	return ((uint32_t)luma_mult & 0xffu) | (((uint32_t)chroma_mult & 0xffu) << 8) | (((uint32_t)offset_scaled & 0xfffu) << 16) | (active ? 0x80000000u : 0u);
+}
+constexpr int model_mix_luma_mult(const uint32_t w) { return (int)(w << 24) >> 24; }
+constexpr int model_mix_chroma_mult(const uint32_t w) { return (int)(w << 16) >> 24; }
+constexpr int model_mix_offset(const uint32_t w) { return (int)(w << 4) >> 20; }
+constexpr int model_mix_active(const uint32_t w) { return (int)(w >> 31); }
 
 // One launch = nframes x (luma workgroups + 2 x chroma workgroups); workgroups are numbered in memory
 // order (frame, plane, block row group, split, column group) and are NOT persistent: the hardware
@@ -296,6 +313,8 @@ struct KernelArgs {
 	// image).  The field sits HERE, in the four bytes that used to be padding in front of the pointer below: the frame table is the kernel
 	// argument BEHIND this structure, so a field appended at the end would move every plane pointer the kernels of before load (the
 	// static_assert below the structure holds its size).
+	// With mix_kernel == 1 as well: the kernels of the mix serve listed frames whose models carry a mix (ModelRecord::mix_flags) -- image, bounds,
+	// shift AND the mix are the frame's model's, `mix` below is not read.
 	int models_kernel;
 	const uint8_t* tables;    // device image (image_layout)
 	uint32_t cur_bit0;        // stream bit of the register of block 0, first block row of the stripe, frame 0
@@ -385,10 +404,13 @@ constexpr bool family_semiplanar(const Family f) { return f != Family::rw && f !
 
 // The family as KernelArgs states it (no kernel reads these three fields; the launcher refuses a key that disagrees with them).  out8 is the
 // key's: it tells sp8 from sp and p2sp8 from p2sp.
+// with_models: a launch of the two families of the mix that names a model per frame (models that carry a mix; the key has neither out8 nor wide) --
+// the same kernels, which decide at run time where the image, the bounds and the mix come from.  Every other family has one answer.
 struct FamilyFields { int models_kernel, mix_kernel, sp_kernel; };
-constexpr FamilyFields family_fields(const Family f)
+constexpr FamilyFields family_fields(const Family f, const bool with_models = false)
 {
-	return FamilyFields{f == Family::ml || f == Family::spml, f == Family::mix || f == Family::sp_mix,
+	const bool mixf = f == Family::mix || f == Family::sp_mix;
+	return FamilyFields{f == Family::ml || f == Family::spml || (mixf && with_models), mixf,
 	                    !family_semiplanar(f) ? 0 : ((f == Family::p2sp || f == Family::p2sp8) ? 2 : 1)};
 }
 

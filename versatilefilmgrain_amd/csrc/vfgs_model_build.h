@@ -36,7 +36,10 @@ struct FwModelJob {
 	int32_t one_y, one_c;     // form of the image (image_layout)
 	int32_t scale_shift;      // the hardware layer's stored shift (vfgs_hw.c:349): pre-shift of the general / wide LUT entries
 	int32_t legal;            // clip_to_restricted_range (host only)
-	int32_t reserved[3];
+	// (host only, vfgs_hip_models_from_afgs1_mix: the bookkeeping turns them into the record's mix words at the programmed depth, and the
+	// kernel writes those with the record; zero = a model without a mix)
+	int32_t mix_carried;      // the model carries a mix
+	uint32_t mix[2];          // Cb, Cr: model_mix_word with the offset as vfgs_hip_set_chroma_mix takes it (not yet << (depth - 8))
 	uint8_t slut[3][256];     // scale bytes of Y, Cb, Cr
 };
 static_assert(sizeof(FwModelJob) % 16 == 0, "jobs of a table are read with aligned scalar and vector loads");

@@ -16,7 +16,8 @@
 
 namespace {
 
-const char* const kWho = "vfgs_hip_models_from_afgs1";
+const char* const kWhoPlain = "vfgs_hip_models_from_afgs1";
+const char* const kWhoMix = "vfgs_hip_models_from_afgs1_mix";
 
 int refuse(int code, const char* fmt, ...)
 {
@@ -29,8 +30,11 @@ int refuse(int code, const char* fmt, ...)
 }
 
 // one parameter set -> the parameter-set side of its job; 0, or the refusal (i: its index in the call, for the message)
-int job_from_afgs1(const fgs_afgs1& p, unsigned i, vfgs::FwModelJob& j)
+// with_mix: the model carries the mix vfgs_init_afgs1 programs with the switch of vfgs_hip_afgs1_chroma_mix on (vfgs_fw_host.cpp), whatever
+// the switch says
+int job_from_afgs1(const fgs_afgs1& p, unsigned i, vfgs::FwModelJob& j, const bool with_mix)
 {
+	const char* const kWho = with_mix ? kWhoMix : kWhoPlain;
 	memset(&j, 0, sizeof j);
 	const int lag = p.ar_coeff_lag;
 	if (lag < 1 || lag > 3)
@@ -62,20 +66,47 @@ int job_from_afgs1(const fgs_afgs1& p, unsigned i, vfgs::FwModelJob& j)
 	j.shift = p.grain_scale_shift + 1;       // vfgs_fw.c:683-686
 	j.scale_shift = p.grain_scaling - 6;     // the argument of vfgs_set_scale_shift; build_models checks and stores it for the programmed depth
 	j.legal = p.clip_to_restricted_range != 0;
-	// cb_mult and the other mix fields: a model carries no mix, whatever vfgs_hip_afgs1_chroma_mix says; grain_seed: the caller's (vfgs_hip_afgs1_seed)
+	// cb_mult and the other mix fields: vfgs_hip_models_from_afgs1 makes models without a mix, whatever vfgs_hip_afgs1_chroma_mix says;
+	// grain_seed: the caller's (vfgs_hip_afgs1_seed)
+	if (with_mix)
+	{
+		// what vfgs_init_afgs1 hands to vfgs_hip_set_chroma_mix, and what that setter would refuse (37 there)
+		const bool cfl = p.chroma_scaling_from_luma != 0;
+		const int v[2][3] = {{cfl ? 64 : p.cb_luma_mult - 128, cfl ? 0 : p.cb_mult - 128, cfl ? 0 : (int)p.cb_offset - 256},
+		                     {cfl ? 64 : p.cr_luma_mult - 128, cfl ? 0 : p.cr_mult - 128, cfl ? 0 : (int)p.cr_offset - 256}};
+		for (int c = 0; c < 2; c++)
+		{
+			if (v[c][0] < -128 || v[c][0] > 127 || v[c][1] < -128 || v[c][1] > 127 || v[c][2] < -256 || v[c][2] > 255)
+				return refuse(42, "%s: parameter set %u: the mix of %s, %d, %d, %d, lies outside -128..127, -128..127, -256..255 (vfgs_hip_set_chroma_mix)", kWho, i,
+				              c ? "Cr" : "Cb", v[c][0], v[c][1], v[c][2]);
+			j.mix[c] = vfgs::model_mix_word(v[c][0], v[c][1], v[c][2], 1);     // (active: the setter's own rule -- a component that was set is)
+		}
+		j.mix_carried = 1;
+	}
 	return 0;
 }
 
-}  // namespace
-
-extern "C" int vfgs_hip_models_from_afgs1(const fgs_afgs1* cfgs, unsigned n, vfgs_hip_model** out, void* stream)
+int models_from(const fgs_afgs1* cfgs, unsigned n, vfgs_hip_model** out, void* stream, const bool with_mix)
 {
+	const char* const kWho = with_mix ? kWhoMix : kWhoPlain;
 	if (n == 0) return 0;
 	if (!out) return refuse(41, "%s: null result pointer for %u models", kWho, n);
 	for (unsigned i = 0; i < n; i++) out[i] = nullptr;
 	if (!cfgs) return refuse(41, "%s: null parameter sets for %u models", kWho, n);
 	std::vector<vfgs::FwModelJob> jobs(n);
 	for (unsigned i = 0; i < n; i++)
-		if (int e = job_from_afgs1(cfgs[i], i, jobs[i])) return e;
+		if (int e = job_from_afgs1(cfgs[i], i, jobs[i], with_mix)) return e;
 	return vfgs::build_models(kWho, jobs.data(), n, out, stream, &vfgs::launch_fw_models);
+}
+
+}  // namespace
+
+extern "C" int vfgs_hip_models_from_afgs1(const fgs_afgs1* cfgs, unsigned n, vfgs_hip_model** out, void* stream)
+{
+	return models_from(cfgs, n, out, stream, false);
+}
+
+extern "C" int vfgs_hip_models_from_afgs1_mix(const fgs_afgs1* cfgs, unsigned n, vfgs_hip_model** out, void* stream)
+{
+	return models_from(cfgs, n, out, stream, true);
 }

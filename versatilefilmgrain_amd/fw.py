@@ -15,7 +15,7 @@ SEI_MAX_MODEL_VALUES = 6   # vfgs_fw.h:49
 EXPORTS = ["vfgs_init_sei", "vfgs_init_afgs1", "vfgs_hip_generate_patterns", "vfgs_hip_get_pattern",
            "vfgs_hip_cfg_defaults", "vfgs_hip_cfg_read", "vfgs_hip_cfg_check", "vfgs_hip_cfg_adjust_chroma",
            "vfgs_hip_cfg_apply_gain", "vfgs_hip_cfg_program", "vfgs_hip_afgs1_chroma_mix", "vfgs_hip_afgs1_seed",
-           "vfgs_hip_models_from_afgs1", "vfgs_hip_models_from_sei"]     # (the calls: hw.VfgsHip.models_from_afgs1, .models_from_sei)
+           "vfgs_hip_models_from_afgs1", "vfgs_hip_models_from_afgs1_mix", "vfgs_hip_models_from_sei"]     # (the calls: hw.VfgsHip.models_from_afgs1, .models_from_afgs1_mix, .models_from_sei)
 
 
 class FgsSei(C.Structure):   # vfgs_fw.h:51-60

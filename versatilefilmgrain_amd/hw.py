@@ -130,6 +130,9 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_get_model_build_stats.restype = None
     lib.vfgs_hip_models_from_afgs1.argtypes = [vp, u, C.POINTER(vp), vp]
     lib.vfgs_hip_models_from_sei.argtypes = [vp, u, C.POINTER(vp), vp]
+    lib.vfgs_hip_models_from_afgs1_mix.argtypes = [vp, u, C.POINTER(vp), vp]
+    lib.vfgs_hip_model_capture_mix.argtypes = [C.POINTER(vp), vp]
+    lib.vfgs_hip_model_chroma_mix.argtypes = [vp, i, C.POINTER(i)]
     lib.vfgs_hip_add_grain_frame_list_models_dev.argtypes = [fp, fp, C.POINTER(vp), sp, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_sp_frame_list_models_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
@@ -201,7 +204,7 @@ EXPORTS = [
     "vfgs_hip_add_grain_frame_list_to_sp_dev", "vfgs_hip_add_grain_frame_list_to_sp8_dev", "vfgs_hip_seed_segments", "vfgs_hip_get_seeded_stream_stats",
     "vfgs_hip_add_grain_frames_host", "vfgs_hip_host_alloc", "vfgs_hip_host_free", "vfgs_hip_last_launch_info",
     "vfgs_hip_set_chroma_mix", "vfgs_hip_clear_chroma_mix", "vfgs_hip_get_chroma_mix", "vfgs_hip_supports_depth",
-    "vfgs_hip_model_capture", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
+    "vfgs_hip_model_capture", "vfgs_hip_model_capture_mix", "vfgs_hip_model_chroma_mix", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
     "vfgs_hip_add_grain_sp_frame_list_models_dev", "vfgs_hip_model_image", "vfgs_hip_get_model_build_stats",
 ]
 
@@ -413,6 +416,33 @@ class VfgsHip:
         out = (C.c_void_p * len(cfgs))()
         self._ck(self.lib.vfgs_hip_models_from_afgs1(arr, len(cfgs), out, stream))
         return list(out)
+
+    def models_from_afgs1_mix(self, cfgs, stream=0):
+        """models_from_afgs1 whose models also CARRY the chroma mix of their parameter set -- what `fw.afgs1_chroma_mix(True);
+        fw.init_afgs1(cfg); model_capture_mix()` would give, whatever the switch says, with the programmed state (mix and switch included)
+        untouched.  The two list calls with a model per picture honour the mix frame by frame.  VfgsHipError as models_from_afgs1, and 42: a mix
+        field set_chroma_mix would refuse; 38: depth 12, or (8 bit) a scaling function that would need the general form."""
+        from . import fw
+        cfgs = list(cfgs)
+        if not cfgs:
+            return []
+        arr = (fw.FgsAfgs1 * len(cfgs))(*cfgs)
+        out = (C.c_void_p * len(cfgs))()
+        self._ck(self.lib.vfgs_hip_models_from_afgs1_mix(arr, len(cfgs), out, stream))
+        return list(out)
+
+    def model_capture_mix(self, stream=0):
+        """model_capture plus the chroma mix that is active now: the model carries it (none active: model_capture's result).  VfgsHipError
+        38 where a processing call would refuse the programmed state under that mix: depth 12, a general-form model."""
+        m = C.c_void_p()
+        self._ck(self.lib.vfgs_hip_model_capture_mix(C.byref(m), stream))
+        return m.value
+
+    def model_chroma_mix(self, m, c):
+        """(luma_mult, chroma_mult, offset, active) of component c (1 = Cb, 2 = Cr) as model m carries them; all zero: no mix."""
+        out = (C.c_int * 4)()
+        self._ck(self.lib.vfgs_hip_model_chroma_mix(m, c, out))
+        return tuple(out)
 
     def models_from_sei(self, cfgs, stream=0):
         """Models straight from FGC SEI messages (fw.FgsSei objects), one kernel launch per 32 of them, at the programmed depth, chroma format
