@@ -431,9 +431,9 @@ void vfgs_hip_get_model_build_stats(uint64_t out[8]);
  * models == NULL, or a NULL or released entry; a model captured at another depth or chroma format than the programmed one; width > 8192
  * (rows walked in parts); an active PROGRAMMED chroma mix ("chroma mix" in the message: a mix reaches this call in its models).  A model
  * that carries a mix adds no refusal of its own: depth and form were checked where the mix was attached.  An empty list is no call at all.
- * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination (with or without a mix),
- * stripe / part forms, host-memory entry points, widths above 8192, persistent luma workgroups (1080p general-form luma runs
- * without them here).  Semi-planar surfaces have the call below. */
+ * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination under a mix (without one:
+ * vfgs_hip_add_grain_frame_list_models_copy8_dev below), stripe / part forms, host-memory entry points, widths above 8192, persistent
+ * luma workgroups (1080p general-form luma runs without them here).  Semi-planar surfaces have the call below. */
 int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
                                              const vfgs_hip_model* const* models,     /* nframes entries */
                                              const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
@@ -462,8 +462,9 @@ int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, con
  * a message that names the cause: models == NULL, a NULL or released entry, a model captured at another depth or chroma format than the
  * programmed one, an active PROGRAMMED chroma mix ("chroma mix" in the message).  Where several apply: the list checks, then 40, then 41.
  * An empty list is no call at all.
- * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination, a planar source, stripe / part
- * forms, host-memory entry points, 4:4:4, widths above 8192. */
+ * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination under a mix (without one:
+ * vfgs_hip_add_grain_sp_frame_list_models_copy8_dev below), a planar source, stripe / part forms, host-memory entry points, 4:4:4,
+ * widths above 8192. */
 int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                                 const vfgs_hip_model* const* models,   /* nframes entries, host memory */
                                                 const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
@@ -471,6 +472,71 @@ int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, co
                                                 unsigned stride, unsigned uv_stride,   /* containers */
                                                 unsigned sample_shift,                 /* 0, or 16 - depth */
                                                 void* stream);
+
+/* A MODEL PER PICTURE WITH THE NARROWED 8-BIT DESTINATION: a player that decodes to 10 or 12 bit, keeps the clean picture as a reference
+ * frame and displays or encodes 8 bit, with film grain parameters that change from picture to picture.  src / stride / cstride exactly as
+ * in vfgs_hip_add_grain_frame_list_copy8_dev (planar pictures at the programmed depth, 10 or 12, in uint16 containers), dst / dst_stride /
+ * dst_cstride exactly as there (planar pictures of bytes, pitches in BYTES, each >= the bytes of a row of whole blocks and a multiple of
+ * 16); models and seeds exactly as in vfgs_hip_add_grain_frame_list_models_dev.  The bytes written -- (uint8)((v + 2) >> 2) of the
+ * grained, clipped sample v at depth 10, (uint8)((v + 8) >> 4) at depth 12 -- the bytes left alone and the four seed registers afterwards
+ * are those of
+ *     for f in list order:
+ *         program the state models[f] was made from;
+ *         if (seeds) vfgs_set_seed(seeds[f]);
+ *         vfgs_hip_add_grain_frame_list_copy8_dev(&src[f], &dst[f], 1, ...)
+ * and the library's own programmed state, its mix included, is UNCHANGED by the call.  Models are the handles of vfgs_hip_model_capture,
+ * vfgs_hip_models_from_afgs1 and vfgs_hip_models_from_sei alike; general-form and one-pattern models are both served, at 4:2:0, 4:2:2,
+ * 4:4:4 and 4:4:0.
+ * Launches: one per run of at most 32 consecutive frames whose models' images share their form (one_y, one_c); a change of form starts a
+ * new launch, a change of patterns, LUTs, scale shift or range does not.  No kernel of their own: the launches are those of the programmed
+ * _copy8 list, whose kernels take image, clip bounds and shift from each frame's model where a launch names models.
+ * vfgs_hip_last_launch_info(): listed = 1, out8 = 1, persistent_luma_workgroups = 0, kernel
+ * grain_rw_kernel<depth,csubx,csuby,true,oney,onec,false,false>, `launches` counts every run.  Inside an overlap region the call
+ * alternates over the two internal streams like every device-pointer call; it runs on the primary device.
+ * Refused before anything changes (a refused call does not reseed).  Where several apply, in this order: everything
+ * vfgs_hip_add_grain_frame_list_copy8_dev refuses for its lists and geometry, with its codes (18 a null list or plane, a destination plane
+ * that shares bytes with another destination plane or with a source plane of another frame; 7; 5 / 6 / 8 source geometry; 15; 6 a
+ * destination pitch that is too small, 8 one that is no multiple of 16) -- except that the scale shift that counts is each model's, checked
+ * where the model was made, and that a null `seeds` selects the single seed sequence; depth 8: 16; then error 41 with a message that names
+ * the cause: models == NULL, a NULL or released entry, a model of another depth or chroma format than the programmed one, width > 8192, an
+ * active PROGRAMMED chroma mix, a model in the list that CARRIES a mix ("chroma mix" in both messages: the kernels of the mix have no
+ * narrowed form with a model per frame).  An empty list is no call at all.
+ * Out of scope, on purpose: models that carry a mix, widths above 8192, stripe / part forms, host-memory entry points, persistent luma
+ * workgroups. */
+int vfgs_hip_add_grain_frame_list_models_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
+                                                   const vfgs_hip_model* const* models,     /* nframes entries, host memory */
+                                                   const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
+                                                   unsigned nframes, unsigned width, unsigned height,
+                                                   unsigned stride, unsigned cstride,            /* source, in 16-bit samples */
+                                                   unsigned dst_stride, unsigned dst_cstride,    /* destination, in bytes */
+                                                   void* stream);
+
+/* ... on SEMI-PLANAR surfaces: P010 / P210 / P012 (or low-aligned containers) in, NV12 / NV16 out, a model with every picture.  src / dst /
+ * the strides / sample_shift exactly as in vfgs_hip_add_grain_sp_frame_list_copy8_dev (never in place), models and seeds as above.  The
+ * bytes written, the bytes left alone and the four seed registers afterwards are those of
+ *     for f in list order:
+ *         program the state models[f] was made from;
+ *         if (seeds) vfgs_set_seed(seeds[f]);
+ *         vfgs_hip_add_grain_sp_frame_list_copy8_dev(&src[f], &dst[f], NULL, 1, ...)
+ * and the library's own programmed state, its mix included, is UNCHANGED.  Launches as above: a run of at most 32 consecutive frames whose
+ * models share (one_y, one_c); vfgs_hip_last_launch_info(): listed = 1, out8 = 1, kernel grain_sp8_kernel<depth,csuby,oney,onec> -- the
+ * kernels of the programmed call, which decide at run time where image, bounds and shift come from; both components of a Cb/Cr byte pair
+ * take the frame's chroma bounds.
+ * Refused before anything changes (a refused call does not reseed).  Where several apply: the list checks of
+ * vfgs_hip_add_grain_sp_frame_list_copy8_dev with its codes (18 a null list or plane, a destination plane that shares bytes with another
+ * destination plane or with ANY source plane of the call, its own frame's included; 7; 5 / 6 / 8; 15; 6 / 8 for dst_stride and
+ * dst_uv_stride), then depth 8: 16, then 40 (csubx != 2, a bad sample_shift, width > 8192), then 41 as above (width aside, which is 40
+ * here).  An empty list is no call at all.
+ * Out of scope, on purpose: models that carry a mix, a planar source (the _to_sp8 call has no form with models), 4:4:4, widths above
+ * 8192, stripe / part forms, host-memory entry points. */
+int vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
+                                                      const vfgs_hip_model* const* models,   /* nframes entries, host memory */
+                                                      const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
+                                                      unsigned nframes, unsigned width, unsigned height,
+                                                      unsigned stride, unsigned uv_stride,          /* source, in 16-bit containers */
+                                                      unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
+                                                      unsigned sample_shift,                 /* 0, or 16 - depth */
+                                                      void* stream);
 
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).

@@ -1653,8 +1653,10 @@ int Launch::admit()
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (p2sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
-	if (mr && (!list || p2sp || dg.out8 || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
+	if (mr && (!list || p2sp || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
 		return fail(19, "internal: a model per frame goes with listed whole frames, planar or semi-planar, of at most %d samples a row, without a programmed chroma mix", vfgs::kTileBlocks * 16);
+	// (the narrowed destination with a model per frame: the OUT8 kernels of rw / sp8 decide at run time; the kernels of the mix have no such form -- refused with 41 at the entry)
+	if (mr && dg.out8 && mr->mix) return fail(19, "internal: models that carry a mix were admitted for a narrowed destination");
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) { nothing = true; return 0; }
 	if (!mr)
@@ -1906,7 +1908,8 @@ int Launch::plan_grid()
 	a.lfronts = (!persist && nframes >= 2 && !in_region && 2 * (yext + (sp ? 1 : 2) * cext) >= (64u << 20)) ? 1 : 0;
 #endif
 	// ... one plane phase apart, but for the launch's last pair (vfgs_layout.h front_phase; grain_rw_kernel only, DESIGN.md 5.0 "a plane phase apart")
-	const vfgs::FrontPhase fp = vfgs::front_phase(a.lfronts, !sp && !p2sp && !mix && !mr, a.pd[0].wgs, a.pd[1].wgs, (int)nframes);
+	// (a model per frame: grain_ml_kernel keeps the fronts in step; with the narrowed destination the launch is grain_rw_kernel's like any other)
+	const vfgs::FrontPhase fp = vfgs::front_phase(a.lfronts, !sp && !p2sp && !mix && (!mr || dg.out8), a.pd[0].wgs, a.pd[1].wgs, (int)nframes);
 	a.front_shift = fp.shift;
 	a.front_plain_from = fp.plain_from;
 	return 0;
@@ -1915,18 +1918,20 @@ int Launch::plan_grid()
 // The launch -- under a chroma mix over shared luma bytes, two of them.
 int Launch::launch()
 {
-	// the kernel of this call (vfgs_layout.h KernelKey), formed once: admit() has refused a model per frame under a mix, with a narrowed destination
-	// or from a planar source, and a planar source under a mix
+	// the kernel of this call (vfgs_layout.h KernelKey), formed once: admit() has refused a model per frame under a programmed mix, models that carry a
+	// mix with a narrowed destination, a model per frame from a planar source onto a surface, and a planar source under a mix
 	using vfgs::Family;
 	key = vfgs::KernelKey{8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist,
 	                      p2sp ? (dg.out8 ? Family::p2sp8 : Family::p2sp)
 	                      : sp ? (mix ? Family::sp_mix : dg.out8 ? Family::sp8 : mr ? Family::spml : Family::sp)
-	                           : (mix ? Family::mix : mr ? Family::ml : Family::rw)};
+	                           : (mix ? Family::mix : (mr && !dg.out8) ? Family::ml : Family::rw)};
 	// (models that carry a mix: the kernels of the mix, which take image, bounds and mix from the frame's model where models_kernel is set)
 	const bool mix_models = mr && mix;
-	if (mr && !mix_models && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
+	// (a model per frame with the narrowed destination: the OUT8 kernels of ordinary rows without persistence, which decide the same way)
+	const bool out8_models = mr && !mix && (key.family == Family::rw || key.family == Family::sp8) && key.out8 && !key.wide && !key.persist;
+	if (mr && !mix_models && !out8_models && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
 	if (mix_models && (key.out8 || key.wide)) return fail(19, "internal: models that carry a mix were admitted for a narrowed destination or rows walked in parts");
-	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models);
+	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models || out8_models);
 	a.models_kernel = ff.models_kernel; a.mix_kernel = ff.mix_kernel; a.sp_kernel = ff.sp_kernel;
 	if (sp || p2sp) a.sp_shift2 = sample_shift * 0x10001u;
 	if (mix)
@@ -3857,6 +3862,69 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
 	const std::vector<vfgs_hip_frame_ptrs> ps = three_planes(src, nframes), pd = three_planes(dst, nframes);
 	ListCall l(ps.data(), pd.data(), nframes, seeds, stream, GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::semiplanar, sample_shift).dst_rows(true, dst_stride, dst_uv_stride));
 	if (int e = check_list(l)) return e;
+	return launch_list(l);
+}
+
+// A MODEL PER FRAME WITH THE NARROWED 8-BIT DESTINATION (vfgs_hip.h): the two calls with models above with the destination geometry of the
+// _copy8 lists.  What both refuse between the list checks and the launches, in the order the header states: the destination's pitches with the
+// codes of the programmed _copy8 list (uv: a UV row of bytes is as long as the luma row), then depth 8 (16).
+static int check_out8_rows(const State& s, unsigned width, unsigned dst_stride, unsigned dst_cstride, bool uv)
+{
+	const unsigned nb16 = (width + 15) / 16 * 16;
+	if (dst_stride < nb16 || dst_cstride < (uv ? nb16 : nb16 / (unsigned)s.csubx)) return fail(6, "destination stride too small");
+	if (dst_stride % 16 || dst_cstride % 16) return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
+	if (s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
+	return 0;
+}
+
+// ... and behind check_models: the kernels of the mix have no narrowed form with models (nframes live models, check_models has seen to that)
+static int check_models_without_mix(const char* who, const vfgs_hip_model* const* models, unsigned nframes)
+{
+	for (unsigned f = 0; f < nframes; f++)
+		if (models[f]->has_mix)
+			return fail(41, "%s: the model of frame %u carries a chroma mix; the kernels of the mix have no narrowed form with a model per frame", who, f);
+	return 0;
+}
+
+int vfgs_hip_add_grain_frame_list_models_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const vfgs_hip_model* const* models,
+                                                   const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                                   unsigned cstride, unsigned dst_stride, unsigned dst_cstride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	const char* const who = "frame list with models, 8-bit destination";
+	ListCall l = ListCall(src, dst, nframes, seeds, stream, GrainCall().rows(width, stride, cstride).whole(height).dst_rows(true, dst_stride, dst_cstride)).with(models);
+	if (int e = check_list(l)) return e;
+	if (int e = check_models_window(l)) return e;
+	if (int e = check_out8_rows(s, width, dst_stride, dst_cstride, false)) return e;
+	if (int e = check_models(who, s, models, nframes, width)) return e;
+	if (int e = check_models_without_mix(who, models, nframes)) return e;
+	return launch_list(l);
+}
+
+int vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst, const vfgs_hip_model* const* models,
+                                                      const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                                      unsigned uv_stride, unsigned dst_stride, unsigned dst_uv_stride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	if (!src || !dst) return fail(18, "frame list: null list");
+	const char* const who = "semi-planar frames with models, 8-bit destination";
+	const std::vector<vfgs_hip_frame_ptrs> ps = three_planes(src, nframes), pd = three_planes(dst, nframes);     // (never in place: the containers differ in size)
+	ListCall l = ListCall(ps.data(), pd.data(), nframes, seeds, stream,
+	                      GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::semiplanar, sample_shift).dst_rows(true, dst_stride, dst_uv_stride)).with(models);
+	if (int e = check_list(l)) return e;
+	if (int e = check_models_window(l)) return e;
+	if (int e = check_out8_rows(s, width, dst_stride, dst_uv_stride, true)) return e;
+	if (int e = check_semiplanar(who, s, sample_shift, width)) return e;
+	if (int e = check_models(who, s, models, nframes, 0)) return e;
+	if (int e = check_models_without_mix(who, models, nframes)) return e;
 	return launch_list(l);
 }
 

@@ -693,6 +693,8 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     KernelArgs::models_kernel, a wave-uniform branch around the scalar loads -- the same kernel serves the programmed mix (the launch's
 //     values) and listed frames whose models carry a mix of their own (the frame's values; MIX: the mix words of its record too, not
 //     KernelArgs::mix).  A value of its own so that the instantiations every other kernel uses stay what they were.
+//     MODELS = 2 with OUT8 (every plane of grain_rw_kernel<.., OUT8, .., !WIDE, !PERSIST>, the luma planes of grain_sp8_kernel): the same
+//     run-time decision for the narrowed destination -- the programmed _copy8 calls and the _models_copy8 lists share their kernels.
 template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0, int MODELS = 0>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
@@ -721,7 +723,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
-	static_assert(!MODELS || (!OUT8 && !WIDE && !PERSIST && (!MIX || MODELS == 2) && SP != 2), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup; under the mix: decided at run time");
+	static_assert(!MODELS || (!WIDE && !PERSIST && (!MIX || MODELS == 2) && SP != 2 && (!OUT8 || (MODELS == 2 && !MIX))), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup; under the mix and with the narrowed destination: decided at run time");
 	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
@@ -1241,6 +1243,10 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 	// grid: x = (workgroup inside the frame, frame of a group of 2^lfronts frames), y = group of frames.  Large frames are swept
 	// two at a time: the workgroups of frames 2m and 2m + 1 are dealt out alternately (measured: +1.6 % at 4320p, nothing at 2160p;
 	// more than two, or smaller frames: a loss -- profiles/r03_ab18_frame_fronts_in_one_launch.log)
+	// A model per frame with the narrowed destination (KernelArgs::models_kernel; vfgs_hip_add_grain_frame_list_models_copy8_dev):
+	// the OUT8 kernels of ordinary rows without persistence take image, bounds and shift from the frame's model where the launch names
+	// models, decided at run time (run_plane_rw MODELS = 2) -- no kernel of their own.  Every other instantiation is what it was.
+	constexpr int PM = (OUT8 && !WIDE && !PERSIST) ? 2 : 0;
 	int f, r;
 	if constexpr (PERSIST)
 	{
@@ -1266,7 +1272,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 	}
 	if (f >= a.nframes) return;
 	if (r < a.pd[0].wgs)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, OUT8, WIDE, false>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, OUT8, WIDE, false, false, 0, PM>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
 	{
 		r -= a.pd[0].wgs;
@@ -1274,11 +1280,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64, (rw_waves_per_simd<DEPTH, ONEY, O
 		if (comp == 2) r -= a.pd[1].wgs;
 		// horizontally subsampled chroma rows of one or two positions (2 KiB and less: 1080p at 10 bit, 2160p at 8 bit): several rows per group
 		if (!WIDE && CSUBX == 2 && a.pd[1].rw_segs == 2 && ring_depth<DEPTH, ONEC>() >= 2)      // (a ring of one set cannot hold two positions of a row)
-			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, WIDE ? 0 : 2, OUT8, WIDE, false>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, WIDE ? 0 : 2, OUT8, WIDE, false, false, 0, PM>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
 		else if (!WIDE && CSUBX == 2 && a.pd[1].rw_segs == 1)
-			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, WIDE ? 0 : 1, OUT8, WIDE, false>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, WIDE ? 0 : 1, OUT8, WIDE, false, false, 0, PM>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
 		else
-			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, 0, OUT8, WIDE, false>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
+			run_plane_rw<DEPTH, 16 / CSUBX, CSUBX, CSUBY, L.c_rs, L.c_bytes, ONEC, L.c_neg, 0, OUT8, WIDE, false, false, 0, PM>(a, ft, a.pd[1], lds, comp, f, r, L.c_off[comp - 1], L.c_bank, L.c_lut[comp - 1], lane, wave);
 	}
 }
 
@@ -1387,6 +1393,8 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // through it with scalar loads, in front of the table loads; everything they feed stays wave-uniform.  Without the flag nothing of this exists.
 // MODELS = 2 (UV workgroups of grain_sp_mix_kernel): decided at run time by KernelArgs::models_kernel, as in run_plane_rw -- the frame's model
 // then also supplies both components' mix (the two mix words of its record), and KernelArgs::mix is not read.
+// MODELS = 2 with OUT8 (UV workgroups of grain_sp8_kernel): the same run-time decision without a mix; BOTH components of the 16-byte unit of
+// Cb/Cr byte pairs are clipped with the frame's chroma bounds (lo2 / hi2 below are one pair for the two grain_unit calls of a position).
 template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, int MODELS = 0>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
@@ -1406,7 +1414,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of them belong to the lane before its own
 	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0 && !MIX), "the narrowed destination exists for 16-bit containers, without the mix");
 	static_assert(!PLANAR || !MIX, "a planar source has no mix form");
-	static_assert(!MODELS || (MIX == (MODELS == 2) && !OUT8 && !PLANAR), "a model per frame: the plain UV walk; under the mix: decided at run time");
+	static_assert(!MODELS || (!PLANAR && (OUT8 ? (MODELS == 2 && !MIX) : MIX == (MODELS == 2))), "a model per frame: the plain UV walk; under the mix and with the narrowed destination: decided at run time");
 	constexpr bool DGEO = OUT8 || PLANAR;                // the destination has a geometry of its own
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
@@ -1872,10 +1880,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp8_kernel
 	const int f = (int)(blockIdx.y << a.lfronts) + (int)(blockIdx.x & ((1u << a.lfronts) - 1));
 	const int r = (int)(blockIdx.x >> a.lfronts);
 	if (f >= a.nframes) return;
+	// (a model per frame -- KernelArgs::models_kernel; vfgs_hip_add_grain_sp_frame_list_models_copy8_dev -- is decided at run time in both walks: MODELS = 2)
 	if (r < a.pd[0].wgs)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, true, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, true, false, false, false, true, 2>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
-		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true, false, 2>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // The kernels of a PLANAR source with a semi-planar destination (KernelArgs::sp_kernel == 2; vfgs_hip_add_grain_frame_list_to_sp_dev):
@@ -1976,7 +1985,10 @@ static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const Ke
 	// the narrowed destination nor rows walked in parts)
 	const bool mix_models = (f == Family::mix || f == Family::sp_mix) && a.models_kernel != 0;
 	if (mix_models && (k.out8 || k.wide)) return false;
-	const FamilyFields ff = family_fields(f, mix_models);
+	// (so do the narrowed kernels of ordinary rows without persistence: grain_rw_kernel<.., out8, .., !wide, !persist> and grain_sp8_kernel)
+	const bool out8_models = (f == Family::rw || f == Family::sp8) && a.models_kernel != 0;
+	if (out8_models && !(k.out8 && !k.wide && !k.persist)) return false;
+	const FamilyFields ff = family_fields(f, mix_models || out8_models);
 	if (a.models_kernel != ff.models_kernel || a.mix_kernel != ff.mix_kernel || a.sp_kernel != ff.sp_kernel) return false;
 	if (k.wide != (a.nblk > kTileBlocks)) return false;
 	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return false;

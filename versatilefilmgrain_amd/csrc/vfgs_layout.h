@@ -315,6 +315,8 @@ struct KernelArgs {
 	// static_assert below the structure holds its size).
 	// With mix_kernel == 1 as well: the kernels of the mix serve listed frames whose models carry a mix (ModelRecord::mix_flags) -- image, bounds,
 	// shift AND the mix are the frame's model's, `mix` below is not read.
+	// With a key of family rw or sp8 that has out8 (neither wide nor persist): the narrowed kernels serve listed frames with a model each the same way
+	// (vfgs_hip_add_grain_frame_list_models_copy8_dev, vfgs_hip_add_grain_sp_frame_list_models_copy8_dev).
 	int models_kernel;
 	const uint8_t* tables;    // device image (image_layout)
 	uint32_t cur_bit0;        // stream bit of the register of block 0, first block row of the stripe, frame 0
@@ -405,12 +407,14 @@ constexpr bool family_semiplanar(const Family f) { return f != Family::rw && f !
 // The family as KernelArgs states it (no kernel reads these three fields; the launcher refuses a key that disagrees with them).  out8 is the
 // key's: it tells sp8 from sp and p2sp8 from p2sp.
 // with_models: a launch of the two families of the mix that names a model per frame (models that carry a mix; the key has neither out8 nor wide) --
-// the same kernels, which decide at run time where the image, the bounds and the mix come from.  Every other family has one answer.
+// the same kernels, which decide at run time where the image, the bounds and the mix come from -- or of rw / sp8 with the narrowed destination
+// (the key has out8, neither wide nor persist; the launcher holds it to that): the OUT8 kernels decide the same way.  Every other family has one answer.
 struct FamilyFields { int models_kernel, mix_kernel, sp_kernel; };
 constexpr FamilyFields family_fields(const Family f, const bool with_models = false)
 {
 	const bool mixf = f == Family::mix || f == Family::sp_mix;
-	return FamilyFields{f == Family::ml || f == Family::spml || (mixf && with_models), mixf,
+	const bool run_time = mixf || f == Family::rw || f == Family::sp8;     // the families whose kernels serve programmed launches and models alike
+	return FamilyFields{f == Family::ml || f == Family::spml || (run_time && with_models), mixf,
 	                    !family_semiplanar(f) ? 0 : ((f == Family::p2sp || f == Family::p2sp8) ? 2 : 1)};
 }
 
