@@ -177,7 +177,7 @@ typedef struct vfgs_hip_pattern_job {
 	int32_t kind;       /* 0: frequency filtered (vfgs_fw.c:362-408), 1: auto-regressive (vfgs_fw.c:410-502) */
 	int32_t chroma;     /* 0: 64x64 luma pattern, noise seed Seed_LUT[0]; 1: 32x32 chroma pattern */
 	int32_t index;      /* pattern slot 0..7, as vfgs_set_luma_pattern / vfgs_set_chroma_pattern */
-	int32_t seed_index; /* which entry of the seed table starts the noise generator (vfgs_fw.c:369,392,620,...) */
+	int32_t seed_index; /* which entry of the seed table, 0..255, starts the noise generator (vfgs_fw.c:369,392,620,...) */
 	int32_t fh, fv;     /* kind 0: horizontal / vertical cut-off, comp_model_value[1], [2] (2..14) */
 	int32_t scale;      /* kind 1: right shift of the filter sum (log2_scale_factor or ar_coeff_shift), 1..15 */
 	int32_t shift;      /* kind 1: right shift of the Gaussian sample, 1..7 */

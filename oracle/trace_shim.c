@@ -26,8 +26,58 @@ enum {
 
 static FILE* out;
 
+/* In-memory mode, for a process that runs thousands of parameter sets through the firmware (as a shared library,
+ * _ref/libvfgs_fw_trace.so): vfgs_trace_to_memory(1) makes the setters append their records (no file header) to a
+ * buffer instead of the file, vfgs_trace_take() hands the records back and clears it. */
+static int to_memory;
+static unsigned char* mem;
+static size_t mem_len, mem_cap;
+
+void vfgs_trace_to_memory(int on)
+{
+	to_memory = on;
+	mem_len = 0;
+}
+
+/* copies the records gathered since the last call into dst (at most cap bytes) and clears them; returns their size,
+ * which is larger than cap if they did not fit (nothing is copied then) */
+size_t vfgs_trace_take(void* dst, size_t cap)
+{
+	const size_t n = mem_len;
+	if (n <= cap && n)
+		memcpy(dst, mem, n);
+	mem_len = 0;
+	return n;
+}
+
+static void mem_put(const void* p, size_t n)
+{
+	if (mem_len + n > mem_cap)
+	{
+		mem_cap = 2 * (mem_len + n) + 65536;
+		mem = realloc(mem, mem_cap);
+		if (!mem)
+		{
+			fprintf(stderr, "trace_shim: out of memory\n");
+			exit(2);
+		}
+	}
+	memcpy(mem + mem_len, p, n);
+	mem_len += n;
+}
+
 static void rec(unsigned op, int a, int b, const void* payload, unsigned n)
 {
+	if (to_memory)
+	{
+		mem_put(&op, 4);
+		mem_put(&a, 4);
+		mem_put(&b, 4);
+		mem_put(&n, 4);
+		if (n)
+			mem_put(payload, n);
+		return;
+	}
 	if (!out)
 	{
 		const char* name = getenv("VFGS_TRACE_OUT");

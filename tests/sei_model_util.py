@@ -138,6 +138,9 @@ def facts(s):
             tails[c] = []
             continue
         n = s.num_intensity_intervals[c]
+        if n == 0:                      # (present with no interval: nothing to read; none of generated_sei's messages is)
+            tails[c] = []
+            continue
         lows = [int(s.intensity_interval_lower_bound[c][k]) for k in range(n)]
         highs = [int(s.intensity_interval_upper_bound[c][k]) for k in range(n)]
         vals = [_read(s, c, k) for k in range(n)]

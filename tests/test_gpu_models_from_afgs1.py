@@ -19,6 +19,7 @@ import model_list_util as U
 import semiplanar_util as SP
 import sp_model_list_util as SU
 import vfgs_testlib as T
+from fw_space import generated_set         # (the generator lives with the others of the firmware's space; the draws are the same)
 from gpu_util import stream_ptr
 from test_gpu_frame_list import garbage_frame, scattered
 
@@ -121,34 +122,6 @@ def test_reference_truth(hip, geo):
 
 
 # ---- 2. against the capture path, byte for byte ------------------------------------------------------------------------------------
-
-def generated_set(rng):
-    """a valid parameter set over the space a bitstream spans: lag 1..3, shifts, 1..14 / 0..10 scaling points, coefficients over 8 bits"""
-    a = fw().FgsAfgs1()
-    a.grain_seed = int(rng.integers(0, 65536))
-    for pts, vals, scal, lo, mx in (("num_y_points", a.point_y_values, a.point_y_scaling, 1, 14),
-                                    ("num_cb_points", a.point_cb_values, a.point_cb_scaling, 0, 10),
-                                    ("num_cr_points", a.point_cr_values, a.point_cr_scaling, 0, 10)):
-        n = int(rng.integers(lo, mx + 1))
-        setattr(a, pts, n)
-        xs = np.sort(rng.choice(np.arange(0, 256), size=n, replace=False))
-        for k in range(n):
-            vals[k] = int(xs[k])
-            scal[k] = int(rng.integers(0, 256))
-    a.chroma_scaling_from_luma = int(rng.integers(0, 2))
-    a.grain_scaling = int(rng.integers(8, 12))
-    a.ar_coeff_lag = int(rng.integers(1, 4))
-    for arr, n in ((a.ar_coeffs_y, 24), (a.ar_coeffs_cb, 25), (a.ar_coeffs_cr, 25)):
-        for k in range(n):
-            arr[k] = int(rng.integers(-128, 128))
-    a.ar_coeff_shift = int(rng.integers(6, 10))
-    a.grain_scale_shift = int(rng.integers(0, 4))
-    a.clip_to_restricted_range = int(rng.integers(0, 2))
-    # the mix fields are ignored by the call, whatever they hold
-    a.cb_mult, a.cb_luma_mult, a.cb_offset = (int(v) for v in rng.integers(0, 256, 3))
-    a.cr_mult, a.cr_luma_mult, a.cr_offset = (int(v) for v in rng.integers(0, 256, 3))
-    return a
-
 
 def captured(hip, cfg):
     fw().afgs1_chroma_mix(False)

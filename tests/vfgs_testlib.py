@@ -175,7 +175,14 @@ def oracle_lib():
     if _oracle_lib is None:
         if not ORACLE_SO.exists():
             build_oracle()
+        if b"vfgs_fw_oracle_init_sei" not in ORACLE_SO.read_bytes():      # a build from before the firmware oracle (oracle/vfgs_fw_oracle.c)
+            build_oracle()
         lib = C.CDLL(str(ORACLE_SO))
+        for fn in (lib.vfgs_fw_oracle_init_sei, lib.vfgs_fw_oracle_init_afgs1):
+            fn.restype = C.c_long
+            fn.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.vfgs_fw_oracle_pattern.restype = C.c_int
+        lib.vfgs_fw_oracle_pattern.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
         lib.vfgs_oracle_create.restype = C.c_void_p
         lib.vfgs_oracle_lcg_fill.restype = C.c_uint32
         lib.vfgs_oracle_lcg_fill.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_int]

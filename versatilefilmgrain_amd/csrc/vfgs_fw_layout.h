@@ -8,7 +8,8 @@
 namespace vfgs {
 
 constexpr int kFwMaxJobs = 16;        // 8 luma + 8 chroma slots
-constexpr int kFwSeeds = 3;           // seed table entries the firmware starts its generator from (vfgs_fw.c:369,392,689,693,697)
+constexpr int kFwSeeds = 256;         // the whole seed table (vfgs_fw.c:177): the firmware entry points start from entries 0..2
+                                      // (vfgs_fw.c:369,392,689,693,697), a pattern job may name any entry
 constexpr int kFwStreamWords = 192;   // 82*73 generator steps + 11 bits, in 32-bit words, rounded up
 
 // Device image of the constants: fw_tables.bin (oracle/dump_fw_tables.c documents the layout)
