@@ -8,93 +8,15 @@
 // the lines handed over, nothing else).
 //
 // usage: host_walks [walk ...]     (no argument: all of them)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#define WALKS_SEED 1
+#include "walks.h"
 
-#include "../../include/vfgs_hip.h"
-#include "../../include/vfgs_hip_fw.h"
-
-extern "C" void vfgs_stub_stats(uint64_t out[3]);
-extern "C" void vfgs_stub_fail_pinned_allocs(int n);
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipDeviceSynchronize(void);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-
-static int g_fail = 0;
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 1;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-
-// one picture in ordinary host memory, the reference's geometry (yuv.c:54-87): one allocation per plane here, so that a
-// byte written past a plane's end is a heap overflow and not a neighbour's sample
-struct Frame {
-	int w, h, depth, sx, sy, stride, cstride, cw, ch, sz;
-	std::vector<uint8_t> Y, U, V;
-	Frame(int w_, int h_, int depth_, int sx_, int sy_, int stride_ = 0) : w(w_), h(h_), depth(depth_), sx(sx_), sy(sy_)
-	{
-		sz = depth > 8 ? 2 : 1;
-		stride = stride_ ? stride_ : ((w % 64) ? (w + 64) & ~63 : w);
-		cstride = stride / sx;
-		cw = w / sx; ch = (h + sy - 1) / sy;
-		Y.resize((size_t)stride * h * sz); U.resize((size_t)cstride * ch * sz); V.resize((size_t)cstride * ch * sz);
-		fill();
-	}
-	void fill()
-	{
-		for (auto* p : {&Y, &U, &V})
-			for (size_t i = 0; i < p->size(); i += sz)
-			{
-				const uint32_t v = rnd() & ((1u << depth) - 1);
-				(*p)[i] = (uint8_t)v;
-				if (sz == 2) (*p)[i + 1] = (uint8_t)(v >> 8);
-			}
-	}
-	uint8_t* y(int line) { return Y.data() + (size_t)line * stride * sz; }
-	uint8_t* u(int line) { return U.data() + (size_t)(line / sy) * cstride * sz; }
-	uint8_t* v(int line) { return V.data() + (size_t)(line / sy) * cstride * sz; }
-	bool same(const Frame& o) const { return Y == o.Y && U == o.U && V == o.V; }
-};
-
-static void program(int depth, int sx, int sy, bool one_luma, bool one_chroma, unsigned seed = 12345)
+// luma and chroma take their forms apart here, and the seed is this program's own
+static void program_forms(int depth, int sx, int sy, bool one_luma, bool one_chroma)
 {
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		const bool one = c == 0 ? one_luma : one_chroma;
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(5);
-	vfgs_set_seed(seed);
+	Model m{depth, sx, sy, one_luma, one_chroma};
+	m.seed = 12345;
+	program(m);
 }
 
 static void line_loop(Frame& f, int width = 0)
@@ -109,7 +31,7 @@ static void walk_lines_in_order()
 	const int cases[][5] = {{192, 144, 10, 2, 2}, {200, 150, 10, 2, 2}, {192, 144, 8, 1, 1}, {264, 136, 8, 2, 1}, {1920, 1080, 10, 2, 2}, {720, 576, 8, 2, 2}};
 	for (const auto& c : cases)
 	{
-		program(c[2], c[3], c[4], c[2] == 8, true);
+		program_forms(c[2], c[3], c[4], c[2] == 8, true);
 		Frame f(c[0], c[1], c[2], c[3], c[4]);
 		const int nwalks = c[0] > 1000 ? 3 : 5;
 		vfgs_hip_launch_info li0{}, li1{};
@@ -129,7 +51,7 @@ static void walk_lines_in_order()
 
 static void walk_late_edits_and_irregular_calls()
 {
-	program(10, 2, 2, false, true);
+	program_forms(10, 2, 2, false, true);
 	Frame f(320, 176, 10, 2, 2);
 	for (int fi = 0; fi < 4; fi++)
 	{
@@ -161,7 +83,7 @@ static void walk_late_edits_and_irregular_calls()
 
 static void walk_ring_of_stripes()
 {
-	program(10, 2, 2, true, true);
+	program_forms(10, 2, 2, true, true);
 	Frame f(1920, 1080, 10, 2, 2);
 	const int edits[][2] = {{3, 351}, {349, 352}, {350, 704}, {351, 353}, {600, 1079}, {703, 705}, {704, 1056}, {1000, 1057}};
 	for (int fi = 0; fi < 4; fi++)
@@ -191,7 +113,7 @@ static void walk_ring_of_stripes()
 static void walk_declared_frames_and_pitches()
 {
 	// a promised frame: working ahead from the first line of the first walk; then buffers of other pitches and sizes behind it
-	program(8, 2, 2, true, true);
+	program_forms(8, 2, 2, true, true);
 	Frame a(640, 360, 8, 2, 2), b(640, 360, 8, 2, 2, 1024), c(512, 200, 8, 2, 2);
 	OK(vfgs_hip_declare_frame(a.Y.data(), a.U.data(), a.V.data(), a.w, a.h, a.stride, a.cstride));
 	for (int n = 0; n < 3; n++)
@@ -224,7 +146,7 @@ static void walk_host_stripes_and_frames()
 {
 	for (int depth : {8, 10})
 	{
-		program(depth, 2, 2, depth == 8, true);
+		program_forms(depth, 2, 2, depth == 8, true);
 		Frame f(704, 400, depth, 2, 2);
 		Frame before = f;
 		vfgs_add_grain_stripe(f.y(0), f.u(0), f.v(0), 0, f.w, f.h, f.stride, f.cstride);
@@ -264,7 +186,7 @@ static void walk_several_devices()
 {
 	// replicas of the state on further devices (the stub offers two; a device may be listed twice): stripes and host frames are
 	// split by block rows over worker threads
-	program(10, 2, 2, false, true);
+	program_forms(10, 2, 2, false, true);
 	const int two[2] = {0, 1}, three[3] = {0, 1, 0}, one[1] = {0};
 	Frame f(1280, 720, 10, 2, 2);
 	for (int round = 0; round < 2; round++)
@@ -322,7 +244,7 @@ static void walk_device_entries()
 				const int h = w > 4000 ? 48 : 270, sz = depth > 8 ? 2 : 1, stride = (w + 63) & ~63, cstride = stride / sx, ch = (h + sy - 1) / sy;
 				const int nf = 5;
 				const size_t ny = (size_t)stride * h * sz, nc = (size_t)cstride * ch * sz;
-				program(depth, sx, sy, w != 520, true);
+				program_forms(depth, sx, sy, w != 520, true);
 				DevPlanes d(ny * nf, nc * nf);        // frames at a constant pitch: exactly as large as the batch needs
 				OK(vfgs_hip_add_grain_frame_dev(d.Y, d.U, d.V, w, h, stride, cstride, st));
 				OK(vfgs_hip_add_grain_frames_dev(d.Y, d.U, d.V, w, h, stride, cstride, nf, ny, nc, st));
@@ -373,7 +295,7 @@ static void walk_device_entries()
 			}
 		}
 	// a new seed per frame queued behind launches that still read the old stream window; 240 frames through the window refills
-	program(10, 2, 2, false, true);
+	program_forms(10, 2, 2, false, true);
 	{
 		const int w = 1920, h = 1080, stride = 1920, cstride = 960;
 		DevPlanes d((size_t)stride * h * 2 * 8, (size_t)cstride * (h / 2) * 2 * 8);
@@ -398,7 +320,7 @@ static void walk_stripe_batches()
 	// that every window the launch addresses lies inside the image it was handed; the image of the next call is built ahead
 	void* st = nullptr;
 	hipStreamCreateWithFlags(&st, 1);
-	program(10, 2, 2, false, true);
+	program_forms(10, 2, 2, false, true);
 	const int w = 1920, h = 1080, stride = 1920, cstride = 960, nf = 16;
 	uint64_t ss0[4], ss1[4];
 	vfgs_hip_get_stripe_stream_stats(ss0);
@@ -436,7 +358,7 @@ static void walk_lookahead_without_pinned_memory()
 	// (vfgs_host.cpp line_call).  A fresh library state, so that the ring really has to be allocated; the failure is injected into the stub
 	// behind the first walk (line by line: the buffer is not proven yet, the single lines' own bounce buffers get allocated).
 	vfgs_hip_shutdown();
-	program(10, 2, 2, false, true);
+	program_forms(10, 2, 2, false, true);
 	Frame f(1280, 720, 10, 2, 2);
 	Frame before = f;
 	line_loop(f);
@@ -455,7 +377,7 @@ static void walk_lookahead_without_pinned_memory()
 
 static void walk_refusals_and_restart()
 {
-	program(10, 2, 2, false, false);
+	program_forms(10, 2, 2, false, false);
 	DevPlanes d(1 << 20, 1 << 19);
 	CHECK(vfgs_hip_add_grain_frame_dev(d.Y + 8, d.U, d.V, 512, 64, 512, 256, nullptr) == 7);
 	CHECK(vfgs_hip_add_grain_frame_dev(d.Y, d.U, d.V, 128, 64, 128, 64, nullptr) == 5);
@@ -469,15 +391,25 @@ static void walk_refusals_and_restart()
 	uint32_t seeds[4];
 	vfgs_hip_get_seed_state(seeds);
 	vfgs_hip_shutdown();
-	program(8, 2, 2, true, true);
+	program_forms(8, 2, 2, true, true);
 	Frame f(320, 64, 8, 2, 2);
 	line_loop(f);
 	vfgs_hip_shutdown();
 }
 
+// what the model of the HIP runtime has seen so far, behind every walk's line
+static std::string stub_statistics()
+{
+	uint64_t st[3];
+	vfgs_stub_stats(st);
+	char b[128];
+	snprintf(b, sizeof b, "  (stub: %llu operations queued so far, %llu of them deferred copies / launches)", (unsigned long long)st[0], (unsigned long long)st[1]);
+	return b;
+}
+
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	return run_walks(argc, argv, {
 		{"lines_in_order", walk_lines_in_order},
 		{"late_edits", walk_late_edits_and_irregular_calls},
 		{"ring_of_stripes", walk_ring_of_stripes},
@@ -488,20 +420,5 @@ int main(int argc, char** argv)
 		{"stripe_batches", walk_stripe_batches},
 		{"lookahead_without_pinned", walk_lookahead_without_pinned_memory},
 		{"refusals_and_restart", walk_refusals_and_restart},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		uint64_t st[3];
-		vfgs_stub_stats(st);
-		printf("%-28s %s   (stub: %llu operations queued so far, %llu of them deferred copies / launches)\n", w.name, g_fail == before ? "ok" : "FAILED",
-		       (unsigned long long)st[0], (unsigned long long)st[1]);
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();
-	return g_fail ? 1 : 0;
+	}, stub_statistics);
 }

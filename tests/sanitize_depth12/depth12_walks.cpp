@@ -7,106 +7,8 @@
 // (one-pattern models, or launches of few luma tasks); those two paths are the GPU suite's business (tests/test_gpu_depth12.py).
 //
 // usage: depth12_walks [walk ...]     (no argument: all of them)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-
-static int g_fail = 0;
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 12;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-
-struct Frame {
-	int w, h, depth, sx, sy, stride, cstride, ch, sz;
-	std::vector<uint8_t> Y, U, V;
-	Frame(int w_, int h_, int depth_, int sx_, int sy_) : w(w_), h(h_), depth(depth_), sx(sx_), sy(sy_)
-	{
-		sz = depth > 8 ? 2 : 1;
-		stride = (w % 64) ? (w + 64) & ~63 : w;
-		cstride = stride / sx;
-		ch = (h + sy - 1) / sy;
-		Y.resize((size_t)stride * h * sz); U.resize((size_t)cstride * ch * sz); V.resize((size_t)cstride * ch * sz);
-		for (auto* p : {&Y, &U, &V})
-			for (size_t i = 0; i < p->size(); i += sz)
-			{
-				const uint32_t v = rnd() & (sz == 2 ? 0xffffu : 0xffu);     // (a 16-bit container holds anything)
-				(*p)[i] = (uint8_t)v;
-				if (sz == 2) (*p)[i + 1] = (uint8_t)(v >> 8);
-			}
-	}
-	uint8_t* y(int line) { return Y.data() + (size_t)line * stride * sz; }
-	uint8_t* u(int line) { return U.data() + (size_t)(line / sy) * cstride * sz; }
-	uint8_t* v(int line) { return V.data() + (size_t)(line / sy) * cstride * sz; }
-	bool same(const Frame& o) const { return Y == o.Y && U == o.U && V == o.V; }
-};
-
-// exactly as large as the planes: a byte too many is a heap overflow
-struct DevFrame {
-	uint8_t *Y = nullptr, *U = nullptr, *V = nullptr;
-	size_t ny, nc;
-	explicit DevFrame(const Frame& f, int nframes = 1) : ny(f.Y.size()), nc(f.U.size())
-	{
-		hipMalloc((void**)&Y, ny * nframes); hipMalloc((void**)&U, nc * nframes); hipMalloc((void**)&V, nc * nframes);
-		for (int i = 0; i < nframes; i++)
-		{
-			hipMemcpy(Y + i * ny, f.Y.data(), ny, 1); hipMemcpy(U + i * nc, f.U.data(), nc, 1); hipMemcpy(V + i * nc, f.V.data(), nc, 1);
-		}
-	}
-	DevFrame(size_t ny_, size_t nc_) : ny(ny_), nc(nc_) { hipMalloc((void**)&Y, ny); hipMalloc((void**)&U, nc); hipMalloc((void**)&V, nc); }
-	~DevFrame() { hipFree(Y); hipFree(U); hipFree(V); }
-	DevFrame(const DevFrame&) = delete;
-	bool holds(const Frame& f, int i = 0) const
-	{
-		std::vector<uint8_t> y(ny), u(nc), v(nc);
-		hipMemcpy(y.data(), Y + i * ny, ny, 2); hipMemcpy(u.data(), U + i * nc, nc, 2); hipMemcpy(v.data(), V + i * nc, nc, 2);
-		return y == f.Y && u == f.U && v == f.V;
-	}
-};
-
-static void program(int depth, int sx, int sy, bool one_pattern, int shift = 5)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 256);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(shift);
-	vfgs_set_seed(4711);
-}
+#define WALKS_SEED 12
+#include "../sanitize/walks.h"
 
 static bool last_launch(int depth, unsigned long long* launches = nullptr, int* persistent = nullptr)
 {
@@ -317,23 +219,11 @@ static void walk_mix_refused()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	return run_walks(argc, argv, {
 		{"setters_and_export", walk_setters_and_export},
 		{"device_entries", walk_device_entries},
 		{"host_entries", walk_host_entries},
 		{"depth_switches_two_threads", walk_depth_switches_two_threads},
 		{"mix_refused", walk_mix_refused},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();
-	return g_fail ? 1 : 0;
+	});
 }

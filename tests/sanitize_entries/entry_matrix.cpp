@@ -9,47 +9,8 @@
 // ("expr -> text (file:line)"); of such a text only the runtime's part is printed.  The stub knows fewer kernels than the launcher (no
 // narrowed destination and no persistent workgroups at 12 bit): such a call is recorded with the stub's refusal, registers moved and all.
 // Values are the GPU suite's business; addresses are the sanitizer walks' (planes here are allocated generously).
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static uint32_t g_lcg = 7;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-
-static void program(int depth, int sx, int sy, bool one_pattern)
-{
-	vfgs_hip_reset_state();
-	vfgs_hip_clear_chroma_mix();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(5);
-	vfgs_set_seed(4711);
-}
+#define WALKS_SEED 7
+#include "../sanitize/walks.h"
 
 static vfgs_hip_model* capture()
 {
@@ -186,7 +147,7 @@ static std::string describe(const Shape& s, const Args& a, const char* more = ""
 	return b;
 }
 
-static std::vector<uint32_t> seeds_of(unsigned n)
+static std::vector<uint32_t> matrix_seeds(unsigned n)
 {
 	std::vector<uint32_t> s(n);
 	for (unsigned i = 0; i < n; i++) s[i] = i == 0 ? 0 : (i == 1 ? 0x80000000u : 1234567u * i + 89);
@@ -232,7 +193,7 @@ static void matrix()
 				go(turn++ & 1 ? COPY8 : COPY, a);
 				a = base(s, A, B, 3);
 				a.py = py; a.ph = ph;
-				a.seeds = seeds_of(3);
+				a.seeds = matrix_seeds(3);
 				go(SEEDED_PART, a);
 			}
 		// whole frames, in place and copied, with and without a seed per frame, a model per frame: every entry at some frame count
@@ -242,7 +203,7 @@ static void matrix()
 			if (n > nmax) continue;
 			Args a = base(s, A, B, n), c = a, sd = a, sc = a;     // in place, copied, seeded in place, seeded and copied
 			c.copy = sc.copy = true;
-			sd.seeds = sc.seeds = seeds_of(n);
+			sd.seeds = sc.seeds = matrix_seeds(n);
 			go(FRAMES, a);
 			go(LIST, a);
 			go(SEEDED, sd);
@@ -285,7 +246,7 @@ static void modes()
 					if ((narrows(e) && depth == 8) || (copy && !takes_dst(e)) || (!copy && must_copy(e))) continue;
 					Args a = base(s, A, B, e == FRAME ? 1 : 3);
 					a.copy = copy != 0;
-					if (e == SEEDED) a.seeds = seeds_of(3);
+					if (e == SEEDED) a.seeds = matrix_seeds(3);
 					report(e, describe(s, a, more), call(e, a));
 				}
 		}
@@ -453,7 +414,7 @@ static void refusals()
 				Args a = base(s, A, B, 3);
 				a.copy = takes_dst(e);
 				if (parts) { a.py = 16; a.ph = 17; }
-				if (seeded || e >= MODELS) a.seeds = seeds_of(3);
+				if (seeded || e >= MODELS) a.seeds = matrix_seeds(3);
 				if (e == MODELS || e == SP_MODELS) a.models.assign(3, g_live);
 				if (together) apply(order[i + 1], e, a);      // (the earlier one is applied last: where both change one argument, it wins)
 				apply(order[i], e, a);

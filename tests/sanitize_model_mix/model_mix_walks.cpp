@@ -18,19 +18,15 @@
 
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/vfgs_hip.h"
-#include "../../include/vfgs_hip_fw.h"
+#define WALKS_SEED 17
+#define WALKS_HAVE_HIP_RUNTIME_H
+#include "../sanitize/walks.h"
 #include "../../versatilefilmgrain_amd/csrc/vfgs_model_build.h"
 
-static std::atomic<int> g_fail{0};
+using Planes = BarePlanes;
+
 static std::atomic<uint64_t> g_standin_launches{0};
 
 namespace vfgs {
@@ -92,25 +88,12 @@ static bool handed(vfgs::Family f, int models_kernel, int mix_kernel)
 	return g_handed.family == f && g_handed.models_kernel == models_kernel && g_handed.mix_kernel == mix_kernel && g_handed.listed == 1 && !g_handed.out8 && !g_handed.wide;
 }
 
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
 // the three entry points exist with these C types
 static_assert(std::is_same<decltype(&vfgs_hip_models_from_afgs1_mix), int (*)(const fgs_afgs1*, unsigned, vfgs_hip_model**, void*)>::value, "vfgs_hip_models_from_afgs1_mix");
 static_assert(std::is_same<decltype(&vfgs_hip_model_capture_mix), int (*)(vfgs_hip_model**, void*)>::value, "vfgs_hip_model_capture_mix");
 static_assert(std::is_same<decltype(&vfgs_hip_model_chroma_mix), int (*)(const vfgs_hip_model*, int, int*)>::value, "vfgs_hip_model_chroma_mix");
 static_assert(sizeof(vfgs::ModelRecord) == 32 && offsetof(vfgs::ModelRecord, mix_flags) == 20 && offsetof(vfgs::ModelRecord, mix) == 24, "the record's mix words");
 static_assert(sizeof(vfgs::KernelArgs) == 312 && offsetof(vfgs::FrameTable, model) == 6 * 8 * vfgs::kListFrames, "what the kernels of before load has not moved");
-
-static uint32_t g_lcg = 17;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
 
 // a valid parameter set whose image is all-one-pattern at every depth; the mix fields as given
 static fgs_afgs1 make_set(int cb_mult, int cb_luma, int cb_off, int cr_mult, int cr_luma, int cr_off, bool cfl = false, bool hot = false)
@@ -132,13 +115,6 @@ static fgs_afgs1 make_set(int cb_mult, int cb_luma, int cb_off, int cr_mult, int
 	a.cb_mult = (uint8_t)cb_mult; a.cb_luma_mult = (uint8_t)cb_luma; a.cb_offset = (uint16_t)cb_off;
 	a.cr_mult = (uint8_t)cr_mult; a.cr_luma_mult = (uint8_t)cr_luma; a.cr_offset = (uint16_t)cr_off;
 	return a;
-}
-
-static void set_format(int depth, int sx, int sy)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
 }
 
 struct Snapshot {      // what no call here may change
@@ -171,38 +147,6 @@ static bool mix_is(const vfgs_hip_model* m, int c, int lm, int cm, int off, int 
 	int v[4] = {9, 9, 9, 9};
 	OK(vfgs_hip_model_chroma_mix(m, c, v));
 	return v[0] == lm && v[1] == cm && v[2] == off && v[3] == active;
-}
-
-struct Planes {
-	int stride, cstride;
-	std::vector<uint8_t*> dev;
-	std::vector<vfgs_hip_frame_ptrs> list;
-	std::vector<vfgs_hip_sp_frame> sp_list;
-	Planes(int n, int w, int h, int depth, int sx, int sy, bool semiplanar)
-	{
-		const int sz = depth > 8 ? 2 : 1, ch = (h + sy - 1) / sy;
-		stride = (w + 63) & ~63;
-		cstride = semiplanar ? stride : stride / sx;
-		for (int i = 0; i < n; i++)
-		{
-			uint8_t *Y = nullptr, *U = nullptr, *V = nullptr;
-			hipMalloc((void**)&Y, (size_t)stride * h * sz);
-			hipMalloc((void**)&U, (size_t)cstride * ch * sz);
-			dev.push_back(Y); dev.push_back(U);
-			if (semiplanar) { sp_list.push_back({Y, U}); continue; }
-			hipMalloc((void**)&V, (size_t)cstride * ch * sz);
-			dev.push_back(V);
-			list.push_back({Y, U, V});
-		}
-	}
-	~Planes() { for (uint8_t* p : dev) hipFree(p); }
-	Planes(const Planes&) = delete;
-};
-
-static unsigned long long launches()
-{
-	vfgs_hip_launch_info li;
-	return vfgs_hip_last_launch_info(&li) ? 0 : li.launches;
 }
 
 static bool last_kernel_begins(const char* name)
@@ -270,7 +214,6 @@ static void walk_record()
 		for (vfgs_hip_model* x : m) vfgs_hip_model_release(x);
 		for (vfgs_hip_model* x : p) vfgs_hip_model_release(x);
 	}
-	printf("walk record ok \n");
 }
 
 // runs: at most 32 consecutive frames whose models share (one_y, one_c, carries a mix); the kernel of each run; in place under a mix: two launches
@@ -332,7 +275,6 @@ static void walk_runs()
 			vfgs_hip_model_release(mm[0]); vfgs_hip_model_release(mm[1]); vfgs_hip_model_release(pl[0]);
 		}
 	hipStreamDestroy(s);
-	printf("walk runs ok \n");
 }
 
 static void refused_build(std::vector<fgs_afgs1> sets, unsigned at, int code)
@@ -437,19 +379,13 @@ static void walk_refusals()
 	OK(vfgs_hip_add_grain_frame_list_models_dev(p.list.data(), p.list.data(), ms, nullptr, 1, 264, 40, p.stride, p.cstride, nullptr));
 	hipStreamSynchronize(nullptr);
 	vfgs_hip_model_release(m);
-	printf("walk refusals ok \n");
 }
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {{"record", walk_record}, {"runs", walk_runs}, {"refusals", walk_refusals}};
-	for (auto& w : walks)
-	{
-		bool run = argc == 1;
-		for (int i = 1; i < argc; i++) run = run || !strcmp(argv[i], w.name);
-		if (run) w.fn();
-	}
-	vfgs_hip_shutdown();
-	if (g_fail) { printf("FAILED: %d checks\n", g_fail.load()); return 1; }
-	return 0;
+	return run_walks(argc, argv, {
+		{"record", walk_record},
+		{"runs", walk_runs},
+		{"refusals", walk_refusals},
+	});
 }

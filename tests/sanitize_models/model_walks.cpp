@@ -12,141 +12,10 @@
 // suite's business (tests/test_gpu_model_list.py); the seed registers are compared with those of the contract's loop through the same library.
 //
 // usage: model_walks [walk ...]     (no argument: all of them)
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <thread>
-#include <vector>
+#define WALKS_SEED 41
+#include "../sanitize/walks.h"
 
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static std::atomic<int> g_fail{0};
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 41;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
-
-struct Frame {
-	int w, h, sx, sy, stride, cstride, ch, sz;
-	std::vector<uint8_t> Y, U, V;
-	Frame(int w_, int h_, int depth, int sx_, int sy_) : w(w_), h(h_), sx(sx_), sy(sy_)
-	{
-		sz = depth > 8 ? 2 : 1;
-		stride = (w % 64) ? (w + 64) & ~63 : w;
-		cstride = stride / sx;
-		ch = (h + sy - 1) / sy;
-		Y.resize((size_t)stride * h * sz); U.resize((size_t)cstride * ch * sz); V.resize((size_t)cstride * ch * sz);
-		for (auto* p : {&Y, &U, &V})
-			for (auto& b : *p) b = (uint8_t)rnd();
-	}
-};
-
-// exactly as large as the planes: a byte too many is a heap overflow
-struct DevFrame {
-	uint8_t *Y = nullptr, *U = nullptr, *V = nullptr;
-	size_t ny, nc;
-	explicit DevFrame(const Frame& f) : ny(f.Y.size()), nc(f.U.size())
-	{
-		hipMalloc((void**)&Y, ny); hipMalloc((void**)&U, nc); hipMalloc((void**)&V, nc);
-		hipMemcpy(Y, f.Y.data(), ny, 1); hipMemcpy(U, f.U.data(), nc, 1); hipMemcpy(V, f.V.data(), nc, 1);
-	}
-	~DevFrame() { hipFree(Y); hipFree(U); hipFree(V); }
-	DevFrame(const DevFrame&) = delete;
-	bool holds(const Frame& f) const
-	{
-		std::vector<uint8_t> y(ny), u(nc), v(nc);
-		hipMemcpy(y.data(), Y, ny, 2); hipMemcpy(u.data(), U, nc, 2); hipMemcpy(v.data(), V, nc, 2);
-		return y == f.Y && u == f.U && v == f.V;
-	}
-};
-
-struct Pool {
-	std::vector<std::unique_ptr<DevFrame>> fr;
-	std::vector<vfgs_hip_frame_ptrs> list;
-	Pool(const Frame& f, int n)
-	{
-		for (int i = 0; i < n; i++) { fr.emplace_back(new DevFrame(f)); list.push_back({fr.back()->Y, fr.back()->U, fr.back()->V}); }
-	}
-	bool all_hold(const Frame& f) const
-	{
-		for (const auto& d : fr) if (!d->holds(f)) return false;
-		return true;
-	}
-};
-
-// (callers hold no lock: the walks that program from several threads do not use this)
-static void program(int depth, int sx, int sy, bool one_pattern, int shift = 5, int legal = 0)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(shift);
-	vfgs_set_legal_range(legal);
-	vfgs_set_seed(4711);
-}
-
-static vfgs_hip_model* capture(void* stream)
-{
-	vfgs_hip_model* m = nullptr;
-	OK(vfgs_hip_model_capture(&m, stream));
-	CHECK(m != nullptr);
-	return m;
-}
-
-// what the stub's kernel does not read: the model's device bytes, all of them (the device pointer is the handle's first member)
-static void touch_model(const vfgs_hip_model* m)
-{
-	int info[8];
-	OK(vfgs_hip_model_info(m, info));
-	const uint8_t* dev;
-	memcpy(&dev, m, sizeof dev);
-	std::vector<uint8_t> b((size_t)info[7]);
-	hipMemcpy(b.data(), dev, b.size(), 2);
-	unsigned x = 0;
-	for (uint8_t v : b) x += v;
-	CHECK(info[7] > 4096 && x != 0);
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
+using Pool = FramePool;
 
 // the registers the contract's loop leaves -- they depend on the seeds and the geometry, not on the model -- through the plain entries
 static Regs loop_regs(const Frame& f, int n, const std::vector<uint32_t>* seeds)
@@ -159,19 +28,6 @@ static Regs loop_regs(const Frame& f, int n, const std::vector<uint32_t>* seeds)
 	}
 	hipDeviceSynchronize();
 	return Regs();
-}
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	return s;
-}
-
-static unsigned long long launches()
-{
-	vfgs_hip_launch_info li;
-	return vfgs_hip_last_launch_info(&li) == 0 ? li.launches : 0;
 }
 
 // ---- walks ---------------------------------------------------------------------------------------------------------------
@@ -413,23 +269,12 @@ static void walk_threads()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	// run_walks shuts down with live models (walk_refusals leaves four)
+	return run_walks(argc, argv, {
 		{"orders", walk_orders},
 		{"lists", walk_lists},
 		{"overlap_region", walk_overlap_region},
 		{"refusals", walk_refusals},
 		{"threads", walk_threads},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();         // with live models (walk_refusals leaves four)
-	return g_fail ? 1 : 0;
+	});
 }

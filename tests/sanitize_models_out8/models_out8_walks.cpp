@@ -14,38 +14,8 @@
 // list calls on planar frames of the same size, through the same library.
 //
 // usage: models_out8_walks [walk ...]     (no argument: all of them)
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <vector>
-
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static std::atomic<int> g_fail{0};
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 59;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
+#define WALKS_SEED 59
+#include "../sanitize/walks.h"
 
 // The geometry of one call, planar or semi-planar (sp: U is the plane of Cb/Cr pairs, V unused): sources of 10-bit samples in 16-bit
 // containers, destinations of bytes; every plane (rows - 1) pitches and one row of whole blocks.
@@ -149,93 +119,9 @@ static Planes filled_like(const Geo& g)
 	return d;
 }
 
-static void program(int depth, int sx, int sy, bool one_pattern, int shift = 5, int legal = 0)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(shift);
-	vfgs_set_legal_range(legal);
-	vfgs_set_seed(4711);
-}
-
-static vfgs_hip_model* capture(void* stream)
-{
-	vfgs_hip_model* m = nullptr;
-	OK(vfgs_hip_model_capture(&m, stream));
-	CHECK(m != nullptr);
-	return m;
-}
-
-// what the stub's kernel does not read: the model's device bytes, all of them (the device pointer is the handle's first member)
-static void touch_model(const vfgs_hip_model* m)
-{
-	int info[8];
-	OK(vfgs_hip_model_info(m, info));
-	const uint8_t* dev;
-	memcpy(&dev, m, sizeof dev);
-	std::vector<uint8_t> b((size_t)info[7]);
-	hipMemcpy(b.data(), dev, b.size(), 2);
-	unsigned x = 0;
-	for (uint8_t v : b) x += v;
-	CHECK(info[7] > 4096 && x != 0);
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
-
 // the registers the contract's loop leaves -- they depend on the seeds and the geometry, not on the model or the destination -- through the
 // planar list calls on planar pictures of the same size
-static Regs planar_regs(const Geo& g, int n, const uint32_t* seeds)
-{
-	const size_t cs = g.yrow;
-	std::vector<uint8_t*> mem;
-	std::vector<vfgs_hip_frame_ptrs> l;
-	for (int i = 0; i < n; i++)
-	{
-		uint8_t *y, *u, *v;
-		hipMalloc((void**)&y, (size_t)g.h * g.yrow * 2); hipMalloc((void**)&u, g.crows * cs * 2); hipMalloc((void**)&v, g.crows * cs * 2);
-		mem.insert(mem.end(), {y, u, v});
-		l.push_back({y, u, v});
-	}
-	if (seeds) OK(vfgs_hip_add_grain_frame_list_seeded_dev(l.data(), seeds, n, g.w, g.h, (unsigned)g.yrow, (unsigned)cs, nullptr));
-	else OK(vfgs_hip_add_grain_frame_list_dev(l.data(), n, g.w, g.h, (unsigned)g.yrow, (unsigned)cs, nullptr));
-	hipDeviceSynchronize();
-	for (auto* p : mem) hipFree(p);
-	return Regs();
-}
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	if (n > 2) { s[0] = 0; s[1] = 0x80000000u; }
-	return s;
-}
-
-static unsigned long long launches()
-{
-	vfgs_hip_launch_info li;
-	return vfgs_hip_last_launch_info(&li) == 0 ? li.launches : 0;
-}
+static Regs planar_regs(const Geo& g, int n, const uint32_t* seeds) { return planar_regs(g.w, g.h, g.crows, 2, n, seeds); }
 
 // the entry of the geometry's kind
 static int call(const Geo& g, const Pool& src, const Pool& dst, const vfgs_hip_model* const* ms, const uint32_t* seeds, unsigned n, void* st, unsigned shift = 0)
@@ -458,21 +344,10 @@ static void walk_refusals()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	// run_walks shuts down with live models (walk_refusals leaves ten)
+	return run_walks(argc, argv, {
 		{"runs_across_forms", walk_runs_across_forms},
 		{"release_right_after_the_call", walk_release_right_after_the_call},
 		{"refusals", walk_refusals},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-32s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();         // with live models (walk_refusals leaves ten)
-	return g_fail ? 1 : 0;
+	});
 }

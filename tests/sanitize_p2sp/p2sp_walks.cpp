@@ -21,38 +21,8 @@
 // are compared with those of the planar copy lists on the same sources, through the same library.  Values are the GPU suite's business.
 //
 // usage: p2sp_walks [walk ...]     (no argument: all of them)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <thread>
-#include <vector>
-
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static int g_fail = 0;
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 4242;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
+#define WALKS_SEED 4242
+#include "../sanitize/walks.h"
 
 // a picture of `sz`-byte containers, its planes exactly as large as the contract says.  planar: Y, U, V (C[0], C[1]), a chroma row of 8
 // containers per block; else Y and UV (C[0]), a UV row of 16.  pad / cpad: containers a row pitch exceeds the whole blocks by
@@ -148,44 +118,6 @@ static Pic modelled(const Pic& src, const Pic& fill, bool out8)
 	return out;
 }
 
-static void program(int depth, int sy, bool one_pattern)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(2, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(5);
-	vfgs_set_seed(4711);
-}
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	if (n > 2) { s[0] = 0; s[1] = 0x80000000u; }
-	return s;
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
-
 // the registers the contract names: those of the planar copy list (seeded or not) on the same sources, into planar destinations of their own
 static Regs planar_regs(const Pic& f, int n, const uint32_t* seeds)
 {
@@ -226,7 +158,7 @@ static void walk_both_entry_points()
 		const int depth = c[0], w = c[2], h = c[3], sy = c[4], n = 5;
 		const bool out8 = c[1] != 0;
 		const unsigned shift = (unsigned)c[6];
-		program(depth, sy, c[5] != 0);
+		program(depth, 2, sy, c[5] != 0);
 		Pic f(true, w, h, sy, depth > 8 ? 2 : 1, c[7], c[8]), fill(false, w, h, sy, (depth > 8 && !out8) ? 2 : 1, c[9], c[10]);
 		const Pic want = modelled(f, fill, out8);
 		const std::vector<uint32_t> seeds = seeds_of(n);
@@ -264,7 +196,7 @@ static void walk_thirty_five_frames()
 {
 	for (int out8 = 0; out8 < 2; out8++)
 	{
-		program(10, 2, true);
+		program(10, 2, 2, true);
 		Pic f(true, 264, 40, 2, 2), fill(false, 264, 40, 2, out8 ? 1 : 2, 16, 32);
 		const Pic want = modelled(f, fill, out8 != 0);
 		const std::vector<uint32_t> seeds = seeds_of(35);
@@ -292,7 +224,7 @@ static void walk_overlap_region()
 {
 	void* st = nullptr;
 	hipStreamCreateWithFlags(&st, 1);
-	program(10, 2, true);
+	program(10, 2, 2, true);
 	Pic f(true, 520, 70, 2, 2), fill(false, 520, 70, 2, 2, 0, 16), fill8(false, 520, 70, 2, 1, 16, 0);
 	const Pic want = modelled(f, fill, false), want8 = modelled(f, fill8, true);
 	const std::vector<uint32_t> sb = seeds_of(3);
@@ -318,7 +250,7 @@ static void walk_refusals()
 {
 	for (int out8 = 0; out8 < 2; out8++)
 	{
-		program(10, 2, false);
+		program(10, 2, 2, false);
 		Pic f(true, 520, 70, 2, 2, 0, 0), fill(false, 520, 70, 2, out8 ? 1 : 2, 16, 32);
 		SrcPool pool(f, 3);
 		DstPool other(fill, 3);
@@ -397,7 +329,7 @@ static void walk_refusals()
 			CHECK(call(L.data(), E.data()) == 0);
 			hipDeviceSynchronize();
 			hipFree(arena);
-			program(10, 2, false);
+			program(10, 2, 2, false);
 		}
 		const Regs before;
 		const bool had = vfgs_hip_last_launch_info(&a) == 0;
@@ -433,7 +365,7 @@ static void walk_two_threads()
 {
 	// two threads, pools and a stream each, calling at once: the library serialises them; with a seed per picture the registers a thread's
 	// last call leaves do not show the order as long as both end on the same seed
-	program(10, 2, true);
+	program(10, 2, 2, true);
 	Pic f(true, 520, 70, 2, 2), fill(false, 520, 70, 2, 2, 16, 0), fill8(false, 520, 70, 2, 1, 0, 16);
 	const std::vector<uint32_t> seeds = seeds_of(6);
 	const Regs want = planar_regs(f, 6, seeds.data());
@@ -460,23 +392,11 @@ static void walk_two_threads()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	return run_walks(argc, argv, {
 		{"both_entry_points", walk_both_entry_points},
 		{"thirty_five_frames", walk_thirty_five_frames},
 		{"overlap_region", walk_overlap_region},
 		{"refusals", walk_refusals},
 		{"two_threads", walk_two_threads},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();
-	return g_fail ? 1 : 0;
+	});
 }

@@ -7,130 +7,18 @@
 // (vfgs_set_seed(seeds[f]); vfgs_hip_add_grain_frame_dev(frame f)) run through the same library.  Values are the GPU suite's business.
 //
 // usage: seeded_walks [walk ...]     (no argument: all of them)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <vector>
+#define WALKS_SEED 34
+#include "../sanitize/walks.h"
 
-#include "../../include/vfgs_hip.h"
+using Pool = FramePool;
 
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static int g_fail = 0;
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 34;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
-
-struct Frame {
-	int w, h, sx, sy, stride, cstride, ch, sz;
-	std::vector<uint8_t> Y, U, V;
-	Frame(int w_, int h_, int depth, int sx_, int sy_) : w(w_), h(h_), sx(sx_), sy(sy_)
-	{
-		sz = depth > 8 ? 2 : 1;
-		stride = (w % 64) ? (w + 64) & ~63 : w;
-		cstride = stride / sx;
-		ch = (h + sy - 1) / sy;
-		Y.resize((size_t)stride * h * sz); U.resize((size_t)cstride * ch * sz); V.resize((size_t)cstride * ch * sz);
-		for (auto* p : {&Y, &U, &V})
-			for (auto& b : *p) b = (uint8_t)rnd();
-	}
-};
-
-// exactly as large as the planes: a byte too many is a heap overflow
-struct DevFrame {
-	uint8_t *Y = nullptr, *U = nullptr, *V = nullptr;
-	size_t ny, nc;
-	explicit DevFrame(const Frame& f) : DevFrame(f.Y.size(), f.U.size())
-	{
-		hipMemcpy(Y, f.Y.data(), ny, 1); hipMemcpy(U, f.U.data(), nc, 1); hipMemcpy(V, f.V.data(), nc, 1);
-	}
-	DevFrame(size_t ny_, size_t nc_) : ny(ny_), nc(nc_) { hipMalloc((void**)&Y, ny); hipMalloc((void**)&U, nc); hipMalloc((void**)&V, nc); }
-	~DevFrame() { hipFree(Y); hipFree(U); hipFree(V); }
-	DevFrame(const DevFrame&) = delete;
-	bool holds(const Frame& f) const
-	{
-		std::vector<uint8_t> y(ny), u(nc), v(nc);
-		hipMemcpy(y.data(), Y, ny, 2); hipMemcpy(u.data(), U, nc, 2); hipMemcpy(v.data(), V, nc, 2);
-		return y == f.Y && u == f.U && v == f.V;
-	}
-};
-
-struct Pool {
-	std::vector<std::unique_ptr<DevFrame>> fr;
-	std::vector<vfgs_hip_frame_ptrs> list;
-	Pool(const Frame& f, int n)
-	{
-		for (int i = 0; i < n; i++) { fr.emplace_back(new DevFrame(f)); list.push_back({fr.back()->Y, fr.back()->U, fr.back()->V}); }
-	}
-	std::vector<vfgs_hip_frame_ptrs> at_line(const Frame& f, int y) const
-	{
-		std::vector<vfgs_hip_frame_ptrs> l;
-		for (const auto& d : fr)
-			l.push_back({d->Y + (size_t)y * f.stride * f.sz, d->U + (size_t)(y / f.sy) * f.cstride * f.sz, d->V + (size_t)(y / f.sy) * f.cstride * f.sz});
-		return l;
-	}
-	bool all_hold(const Frame& f) const
-	{
-		for (const auto& d : fr) if (!d->holds(f)) return false;
-		return true;
-	}
-};
-
-static void program(int depth, int sx, int sy, bool one_pattern)
+static std::vector<vfgs_hip_frame_ptrs> at_line(const Pool& pool, const Frame& f, int y)
 {
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(5);
-	vfgs_set_seed(4711);
+	std::vector<vfgs_hip_frame_ptrs> l;
+	for (const auto& d : pool.fr)
+		l.push_back({d->Y + (size_t)y * f.stride * f.sz, d->U + (size_t)(y / f.sy) * f.cstride * f.sz, d->V + (size_t)(y / f.sy) * f.cstride * f.sz});
+	return l;
 }
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	if (n > 2) { s[0] = 0; s[1] = 0x80000000u; }
-	return s;
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
 
 // the registers the contract's loop leaves, through the single-frame entry point of the same library
 static Regs loop_regs(const Frame& f, const std::vector<uint32_t>& seeds)
@@ -176,7 +64,7 @@ static void walk_entries()
 		for (const auto& p : parts)
 		{
 			vfgs_set_seed(7);
-			const auto l = pool.at_line(f, p[0]);
+			const auto l = at_line(pool, f, p[0]);
 			OK(vfgs_hip_add_grain_frame_list_seeded_part_dev(l.data(), seeds.data(), n, w, h, p[0], p[1], f.stride, f.cstride, st));
 			CHECK(Regs() == want);
 		}
@@ -281,7 +169,7 @@ static void walk_interleaved()
 	program(10, 2, 2, true);
 	Frame f(1920, 272, 10, 2, 2);
 	Pool pool(f, 8);
-	const auto part = pool.at_line(f, 64);
+	const auto part = at_line(pool, f, 64);
 	for (int round = 0; round < 3; round++)
 	{
 		const std::vector<uint32_t> seeds = seeds_of(8);
@@ -384,7 +272,7 @@ static void walk_two_devices()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	return run_walks(argc, argv, {
 		{"entries", walk_entries},
 		{"seventy_frames", walk_seventy_frames},
 		{"slot_reuse", walk_slot_reuse},
@@ -392,17 +280,5 @@ int main(int argc, char** argv)
 		{"interleaved", walk_interleaved},
 		{"refusals", walk_refusals},
 		{"two_devices", walk_two_devices},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();
-	return g_fail ? 1 : 0;
+	});
 }

@@ -15,19 +15,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
 
-#include "../../include/vfgs_hip.h"
-#include "../../include/vfgs_hip_fw.h"
+#define WALKS_SEED 43
+#define WALKS_HAVE_HIP_RUNTIME_H
+#include "../sanitize/walks.h"
 #include "../../versatilefilmgrain_amd/csrc/vfgs_model_build.h"
 
-static std::atomic<int> g_fail{0};
+using Planes = BarePlanes;
+
 static std::atomic<uint64_t> g_standin_launches{0}, g_standin_models{0};
 
 namespace vfgs {
@@ -74,19 +69,6 @@ hipError_t launch_fw_models(const FwConstants* k, const FwModelJob* jobs, int n,
 	               [](const FwModelJob& j) { return j.lag >= 1 && j.lag <= 3 && j.scale >= 1 && j.scale <= 15 && j.shift >= 1 && j.shift <= 7; });
 }
 }  // namespace vfgs
-
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 43;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
 
 // a valid message: either kind, 1..12 intervals per component (more than 8 distinct parameter sets happen), chroma components absent at
 // times; `hot`: one interval per component with a scale of 255 at a stored shift of 11+ -- the general form at 8 bit, one-pattern above
@@ -137,68 +119,6 @@ static fgs_afgs1 make_afgs1()
 	a.ar_coeff_shift = 7;
 	return a;
 }
-
-static void set_format(int depth, int sx, int sy, int legal = 0)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	vfgs_set_legal_range(legal);
-}
-
-struct Stats {
-	uint64_t v[8];
-	Stats() { vfgs_hip_get_model_build_stats(v); }
-	bool operator==(const Stats& o) const { return !memcmp(v, o.v, sizeof v); }
-};
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
-
-// every byte of the model through the public read-back, into a buffer of exactly its size; lo: the marker of the stand-in that wrote it
-static void touch_model(const vfgs_hip_model* m, int lo = 0x40)
-{
-	int info[8];
-	OK(vfgs_hip_model_info(m, info));
-	std::vector<uint8_t> b((size_t)info[7]);
-	size_t bytes = 0;
-	OK(vfgs_hip_model_image(m, b.data(), b.size(), &bytes));
-	CHECK(bytes == b.size() && bytes > 4096);
-	int32_t pk = 0;
-	memcpy(&pk, b.data() + 16, 4);
-	CHECK(pk == info[5] && b[32] >= lo && b[32] < lo + 0x20 && b[bytes - 1] == b[32]);      // the record's shift; the stand-in's marker from end to end
-}
-
-// planes of exactly the contract's size; the stub's kernel copies every row the real one addresses
-struct Planes {
-	int w, h, stride, cstride, ch;
-	std::vector<uint8_t*> dev;
-	std::vector<vfgs_hip_frame_ptrs> list;
-	std::vector<vfgs_hip_sp_frame> sp_list;
-	Planes(int n, int w_, int h_, int depth, int sx, int sy, bool semiplanar) : w(w_), h(h_)
-	{
-		const int sz = depth > 8 ? 2 : 1;
-		stride = (w % 64) ? (w + 64) & ~63 : w;
-		cstride = semiplanar ? stride : stride / sx;
-		ch = (h + sy - 1) / sy;
-		for (int i = 0; i < n; i++)
-		{
-			uint8_t *Y = nullptr, *U = nullptr, *V = nullptr;
-			hipMalloc((void**)&Y, (size_t)stride * h * sz);
-			hipMalloc((void**)&U, (size_t)cstride * ch * sz);
-			dev.push_back(Y); dev.push_back(U);
-			if (semiplanar) { sp_list.push_back({Y, U}); continue; }
-			hipMalloc((void**)&V, (size_t)cstride * ch * sz);
-			dev.push_back(V);
-			list.push_back({Y, U, V});
-		}
-	}
-	~Planes() { for (uint8_t* p : dev) hipFree(p); }
-	Planes(const Planes&) = delete;
-};
 
 static std::vector<vfgs_hip_model*> build(const std::vector<fgs_sei>& msgs, void* stream)
 {
@@ -252,13 +172,12 @@ static void walk_sizes()
 				const int arg = msgs[i].log2_scale_factor - (msgs[i].model_id ? 1 : 0);
 				CHECK(info[0] == g[0] && info[1] == g[1] && info[2] == g[2] && info[5] == arg + 6 - (g[0] - 8) && info[6] == g[3]);
 				if (i % 3 == 0) CHECK(info[3] == (g[0] != 8) && info[4] == (g[0] != 8));        // the hot messages: uniform everywhere, general at 8 bit only
-				touch_model(models[i]);
+				touch_image(models[i]);
 			}
 			list_call(models, g[0], g[1], g[2], s);
 			for (vfgs_hip_model* m : models) vfgs_hip_model_release(m);
 		}
 	hipStreamDestroy(s);
-	printf("walk sizes ok \n");
 }
 
 static void walk_release_orders()
@@ -291,7 +210,7 @@ static void walk_release_orders()
 		vfgs_hip_model_release(nullptr);
 		// the next build takes the slabs that were just left -- after their readers -- or new ones; either way the queued launch reads live bytes
 		auto again = build(msgs, s);
-		for (vfgs_hip_model* m : again) touch_model(m);
+		for (vfgs_hip_model* m : again) touch_image(m);
 		hipStreamSynchronize(s2);
 		for (vfgs_hip_model* m : again) vfgs_hip_model_release(m);
 	}
@@ -308,7 +227,6 @@ static void walk_release_orders()
 	}
 	hipStreamDestroy(s);
 	hipStreamDestroy(s2);
-	printf("walk release_orders ok \n");
 }
 
 static void walk_both_list_calls()
@@ -334,11 +252,10 @@ static void walk_both_list_calls()
 			OK(vfgs_hip_add_grain_sp_frame_list_models_dev(p.sp_list.data(), p.sp_list.data(), more.data(), seeds.data(), 7, 264, 40, p.stride, p.cstride, shift, s));
 			OK(vfgs_hip_overlap_end(s));
 			hipStreamSynchronize(s);
-			for (vfgs_hip_model* m : more) { touch_model(m); vfgs_hip_model_release(m); }
+			for (vfgs_hip_model* m : more) { touch_image(m); vfgs_hip_model_release(m); }
 			for (vfgs_hip_model* m : models) vfgs_hip_model_release(m);
 		}
 	hipStreamDestroy(s);
-	printf("walk both_list_calls ok \n");
 }
 
 static void refused(std::vector<fgs_sei> msgs, unsigned at, int code, const char* what)
@@ -391,7 +308,6 @@ static void walk_refusals()
 	CHECK(vfgs_hip_models_from_sei(msgs.data(), 0, out, nullptr) == 0 && out[0] == (vfgs_hip_model*)0x10);      // n == 0: no call at all
 	CHECK(vfgs_hip_models_from_sei(nullptr, 0, nullptr, nullptr) == 0);
 	CHECK(Stats() == s0);
-	printf("walk refusals ok \n");
 }
 
 static void walk_shutdown_and_short_buffer()
@@ -408,7 +324,7 @@ static void walk_shutdown_and_short_buffer()
 	CHECK(vfgs_hip_model_image(models[1], nullptr, 0, &need) == 6 && need == (size_t)info[7]);
 	CHECK(vfgs_hip_model_image(models[1], b.data(), b.size(), nullptr) == 6);
 	CHECK(vfgs_hip_model_image(nullptr, b.data(), b.size(), &need) == 41);
-	touch_model(models[1]);
+	touch_image(models[1]);
 	vfgs_hip_model_release(models[0]);
 	CHECK(vfgs_hip_model_image(models[0], b.data(), b.size(), &need) == 41);
 	// shutdown with live models (and a slab that is partly released): everything goes, the handles are dead, nothing leaks
@@ -418,9 +334,8 @@ static void walk_shutdown_and_short_buffer()
 	// ... and the library starts again
 	set_format(8, 2, 2);
 	auto again = build(make_seis(3, true), nullptr);
-	for (vfgs_hip_model* m : again) { touch_model(m); vfgs_hip_model_release(m); }
+	for (vfgs_hip_model* m : again) { touch_image(m); vfgs_hip_model_release(m); }
 	vfgs_hip_shutdown();
-	printf("walk shutdown_and_short_buffer ok \n");
 }
 
 // the two builders take turns on the pool: a slab left by an AFGS1 build has a staging buffer too short for an SEI job table (the
@@ -438,18 +353,17 @@ static void walk_alternating_pool()
 			std::vector<fgs_afgs1> sets;
 			for (unsigned i = 0; i < (round & 1 ? 32u : 5u); i++) sets.push_back(make_afgs1());
 			auto a = build_afgs1(sets, s);
-			for (vfgs_hip_model* m : a) touch_model(m, 0x80);
+			for (vfgs_hip_model* m : a) touch_image(m, 0x80);
 			if (round % 3 != 2) for (vfgs_hip_model* m : a) vfgs_hip_model_release(m);      // an idle AFGS1 slab in front of the SEI build
 			auto b = build(make_seis(round & 2 ? 32 : 9, true), s);
-			for (vfgs_hip_model* m : b) touch_model(m);
-			if (round % 3 == 2) { for (vfgs_hip_model* m : a) touch_model(m, 0x80); for (vfgs_hip_model* m : a) vfgs_hip_model_release(m); }
+			for (vfgs_hip_model* m : b) touch_image(m);
+			if (round % 3 == 2) { for (vfgs_hip_model* m : a) touch_image(m, 0x80); for (vfgs_hip_model* m : a) vfgs_hip_model_release(m); }
 			std::vector<vfgs_hip_model*> both(b);
 			list_call(both, depth, 2, 2, s);
 			for (vfgs_hip_model* m : b) vfgs_hip_model_release(m);      // an idle SEI slab in front of the next AFGS1 build
 		}
 	}
 	hipStreamDestroy(s);
-	printf("walk alternating_pool ok \n");
 }
 
 static void walk_threads()
@@ -464,7 +378,7 @@ static void walk_threads()
 		hipStreamCreateWithFlags(&s, 0);
 		while (!stop)
 		{
-			lcg = lcg * 1664525u + 1013904223u;
+			lcg = lcg_step(lcg);
 			const unsigned n = 1 + (lcg >> 8) % 40;
 			std::vector<vfgs_hip_model*> out(n);
 			if (afgs1_too && (lcg >> 20 & 1))
@@ -494,24 +408,19 @@ static void walk_threads()
 	stop = true;
 	t1.join();
 	t2.join();
-	for (vfgs_hip_model* m : models) { touch_model(m); vfgs_hip_model_release(m); }
+	for (vfgs_hip_model* m : models) { touch_image(m); vfgs_hip_model_release(m); }
 	hipStreamDestroy(s);
-	printf("walk threads ok \n");
 }
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
-		{"sizes", walk_sizes}, {"release_orders", walk_release_orders}, {"both_list_calls", walk_both_list_calls}, {"refusals", walk_refusals},
-		{"alternating_pool", walk_alternating_pool}, {"threads", walk_threads}, {"shutdown_and_short_buffer", walk_shutdown_and_short_buffer},
-	};
-	for (auto& w : walks)
-	{
-		bool run = argc == 1;
-		for (int i = 1; i < argc; i++) run = run || !strcmp(argv[i], w.name);
-		if (run) w.fn();
-	}
-	vfgs_hip_shutdown();
-	if (g_fail) { printf("FAILED: %d checks\n", g_fail.load()); return 1; }
-	return 0;
+	return run_walks(argc, argv, {
+		{"sizes", walk_sizes},
+		{"release_orders", walk_release_orders},
+		{"both_list_calls", walk_both_list_calls},
+		{"refusals", walk_refusals},
+		{"alternating_pool", walk_alternating_pool},
+		{"threads", walk_threads},
+		{"shutdown_and_short_buffer", walk_shutdown_and_short_buffer},
+	});
 }

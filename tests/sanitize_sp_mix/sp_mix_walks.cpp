@@ -7,155 +7,18 @@
 // (tests/test_gpu_semiplanar_mix.py).
 //
 // usage: sp_mix_walks [walk ...]     (no argument: all of them)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <thread>
-#include <vector>
+#define WALKS_SEED 177
+#include "../sanitize/walks.h"
 
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static int g_fail = 0;
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 177;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
-
-// a semi-planar picture, its planes exactly as large as the contract says: (rows - 1) pitches and one row of whole blocks
-struct Pic {
-	int w, h, depth, sy, sz, nblk, stride, uv_stride, crows;
-	std::vector<uint8_t> Y, UV;
-	Pic(int w_, int h_, int depth_, int sy_, int pad = 0) : w(w_), h(h_), depth(depth_), sy(sy_)
-	{
-		sz = depth > 8 ? 2 : 1;
-		nblk = (w + 15) / 16;
-		stride = nblk * 16 + pad;
-		uv_stride = nblk * 16 + pad;
-		crows = (h + sy - 1) / sy;
-		Y.resize(((size_t)(h - 1) * stride + nblk * 16) * sz);
-		UV.resize(((size_t)(crows - 1) * uv_stride + nblk * 16) * sz);
-		for (auto* p : {&Y, &UV})
-			for (auto& b : *p) b = (uint8_t)rnd();
-	}
-};
-
-struct DevPic {
-	uint8_t *Y = nullptr, *UV = nullptr;
-	size_t ny, nc;
-	explicit DevPic(const Pic& f) : ny(f.Y.size()), nc(f.UV.size())
-	{
-		hipMalloc((void**)&Y, ny); hipMalloc((void**)&UV, nc);
-		hipMemcpy(Y, f.Y.data(), ny, 1); hipMemcpy(UV, f.UV.data(), nc, 1);
-	}
-	~DevPic() { hipFree(Y); hipFree(UV); }
-	DevPic(const DevPic&) = delete;
-	bool holds(const Pic& f) const
-	{
-		std::vector<uint8_t> y(ny), c(nc);
-		hipMemcpy(y.data(), Y, ny, 2); hipMemcpy(c.data(), UV, nc, 2);
-		return y == f.Y && c == f.UV;
-	}
-};
-
-struct Pool {
-	std::vector<std::unique_ptr<DevPic>> fr;
-	std::vector<vfgs_hip_sp_frame> list;
-	Pool(const Pic& f, int n)
-	{
-		for (int i = 0; i < n; i++) { fr.emplace_back(new DevPic(f)); list.push_back({fr.back()->Y, fr.back()->UV}); }
-	}
-	bool all_hold(const Pic& f) const
-	{
-		for (const auto& d : fr) if (!d->holds(f)) return false;
-		return true;
-	}
-};
+using Pic = SpPic;
+using Pool = SpPool;
 
 // a model, then the mix: Cb alone, Cr alone or both (bit 0 / bit 1 of `mix`)
-static void program(int depth, int sy, bool one_pattern, int mix)
+static void program_mix(int depth, int sy, bool one_pattern, int mix)
 {
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(2, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(5);
-	vfgs_set_seed(4711);
-	if (mix & 1) OK(vfgs_hip_set_chroma_mix(1, 32, 32, 0));
-	if (mix & 2) OK(vfgs_hip_set_chroma_mix(2, 64, 101, -202));
-}
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	if (n > 2) { s[0] = 0; s[1] = 0x80000000u; }
-	return s;
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
-
-// the registers the contract names: those of the planar copy list (seeded or not) under the same mix, on planar pictures of the same size
-static Regs planar_copy_regs(const Pic& f, int n, const uint32_t* seeds)
-{
-	const size_t cs = (size_t)f.nblk * 16;     // (a planar chroma row pitch of whole 16-byte units at any block count)
-	std::vector<uint8_t*> mem;
-	std::vector<vfgs_hip_frame_ptrs> s, d;
-	for (int i = 0; i < 2 * n; i++)
-	{
-		uint8_t *y, *u, *v;
-		hipMalloc((void**)&y, (size_t)f.h * f.nblk * 16 * f.sz); hipMalloc((void**)&u, f.crows * cs * f.sz); hipMalloc((void**)&v, f.crows * cs * f.sz);
-		memset(y, 0x55, (size_t)f.h * f.nblk * 16 * f.sz); memset(u, 0x55, f.crows * cs * f.sz); memset(v, 0x55, f.crows * cs * f.sz);
-		mem.insert(mem.end(), {y, u, v});
-		(i < n ? s : d).push_back({y, u, v});
-	}
-	if (seeds) OK(vfgs_hip_add_grain_frame_list_seeded_copy_dev(s.data(), d.data(), seeds, n, f.w, f.h, f.nblk * 16, (unsigned)cs, nullptr));
-	else OK(vfgs_hip_add_grain_frame_list_copy_dev(s.data(), d.data(), n, f.w, f.h, f.nblk * 16, (unsigned)cs, nullptr));
-	hipDeviceSynchronize();
-	for (auto* p : mem) hipFree(p);
-	return Regs();
-}
-
-static unsigned long long launches()
-{
-	vfgs_hip_launch_info li;
-	return vfgs_hip_last_launch_info(&li) == 0 ? li.launches : 0;
+	Model m{depth, 2, sy, one_pattern, one_pattern};
+	m.mix = mix;
+	program(m);
 }
 
 static bool sp_mix_kernel_named(const vfgs_hip_launch_info& li, int depth, int sy)
@@ -179,12 +42,12 @@ static void walk_entries()
 	for (const auto& c : cases)
 	{
 		const int w = c[0], h = c[1], depth = c[2], sy = c[3], shift = c[5], n = 5;
-		program(depth, sy, true, c[4]);
-		Pic f(w, h, depth, sy, c[6]);
+		program_mix(depth, sy, true, c[4]);
+		Pic f(w, h, sy, depth > 8 ? 2 : 1, c[6], c[6]);
 		const std::vector<uint32_t> seeds = seeds_of(n);
 		vfgs_set_seed(99);
-		const Regs want_plain = planar_copy_regs(f, n, nullptr);
-		const Regs want_seeded = planar_copy_regs(f, n, seeds.data());
+		const Regs want_plain = planar_regs(f, n, nullptr, PLANAR_LIST_COPY);
+		const Regs want_seeded = planar_regs(f, n, seeds.data(), PLANAR_LIST_COPY);
 		Pool pool(f, n), out(f, n);
 		vfgs_hip_launch_info li;
 		// in place, one seed sequence: UV first, then luma
@@ -232,10 +95,10 @@ static void walk_entries()
 
 static void walk_thirty_five_frames()
 {
-	program(10, 2, true, 3);
-	Pic f(264, 40, 10, 2);
+	program_mix(10, 2, true, 3);
+	Pic f(264, 40, 2, 2);
 	const std::vector<uint32_t> seeds = seeds_of(35);
-	const Regs want = planar_copy_regs(f, 35, seeds.data());
+	const Regs want = planar_regs(f, 35, seeds.data(), PLANAR_LIST_COPY);
 	Pool pool(f, 35), out(f, 35);
 	vfgs_hip_launch_info b;
 	unsigned long long n0 = launches();
@@ -243,7 +106,7 @@ static void walk_thirty_five_frames()
 	CHECK(vfgs_hip_last_launch_info(&b) == 0 && b.launches - n0 == 4 && b.nframes == 3 && b.listed == 1);     // 32 + 3 frames, two launches each
 	CHECK(Regs() == want);
 	vfgs_set_seed(5);
-	const Regs want2 = planar_copy_regs(f, 35, nullptr);
+	const Regs want2 = planar_regs(f, 35, nullptr, PLANAR_LIST_COPY);
 	vfgs_set_seed(5);
 	n0 = launches();
 	OK(vfgs_hip_add_grain_sp_frame_list_dev(pool.list.data(), out.list.data(), nullptr, 35, f.w, f.h, f.stride, f.uv_stride, 6, nullptr));
@@ -257,12 +120,12 @@ static void walk_overlap_region()
 {
 	void* st = nullptr;
 	hipStreamCreateWithFlags(&st, 1);
-	program(8, 2, true, 3);
-	Pic f(520, 70, 8, 2);
+	program_mix(8, 2, true, 3);
+	Pic f(520, 70, 2, 1);
 	const std::vector<uint32_t> sb = seeds_of(3);
 	vfgs_set_seed(3);
-	planar_copy_regs(f, 4, nullptr);
-	const Regs want = planar_copy_regs(f, 3, sb.data());
+	planar_regs(f, 4, nullptr, PLANAR_LIST_COPY);
+	const Regs want = planar_regs(f, 3, sb.data(), PLANAR_LIST_COPY);
 	Pool a(f, 4), b(f, 3);
 	vfgs_set_seed(3);
 	OK(vfgs_hip_overlap_begin(st));
@@ -277,7 +140,7 @@ static void walk_overlap_region()
 
 static void walk_refusals()
 {
-	Pic f(520, 70, 10, 2);
+	Pic f(520, 70, 2, 2);
 	const std::vector<uint32_t> seeds = seeds_of(3);
 	auto refused = [&](Pool& pool, unsigned shift, const char* cause) {
 		const Regs before;
@@ -293,7 +156,7 @@ static void walk_refusals()
 		CHECK(pool.all_hold(f));
 	};
 	// a general-form model under a mix
-	program(10, 2, false, 1);
+	program_mix(10, 2, false, 1);
 	{
 		Pool pool(f, 3);
 		refused(pool, 6, "general-form");
@@ -310,14 +173,14 @@ static void walk_refusals()
 		hipDeviceSynchronize();
 	}
 	// depth 12 under a mix (P012: shift 4)
-	program(12, 2, true, 3);
+	program_mix(12, 2, true, 3);
 	{
 		Pool pool(f, 3);
 		refused(pool, 4, "depth is 12");
 		refused(pool, 0, "depth is 12");
 		// ... and at depth 10 the same model and list are served
 		vfgs_set_depth(10);
-		const Regs want = planar_copy_regs(f, 3, seeds.data());
+		const Regs want = planar_regs(f, 3, seeds.data(), PLANAR_LIST_COPY);
 		vfgs_set_seed(1);
 		OK(vfgs_hip_add_grain_sp_frame_list_dev(pool.list.data(), pool.list.data(), seeds.data(), 3, f.w, f.h, f.stride, f.uv_stride, 6, nullptr));
 		CHECK(Regs() == want);
@@ -339,10 +202,10 @@ static void walk_two_threads()
 {
 	// two threads, a pool and a stream each, calling at once: the library serialises them; with a seed per picture the order does not
 	// show in the registers a thread's last call leaves only if both end on the same seed.  One thread in place, one out of place.
-	program(10, 2, true, 3);
-	Pic f(520, 70, 10, 2);
+	program_mix(10, 2, true, 3);
+	Pic f(520, 70, 2, 2);
 	const std::vector<uint32_t> seeds = seeds_of(6);
-	const Regs want = planar_copy_regs(f, 6, seeds.data());
+	const Regs want = planar_regs(f, 6, seeds.data(), PLANAR_LIST_COPY);
 	Pool pa(f, 6), pb(f, 6), pc(f, 6);
 	void* st[2] = {nullptr, nullptr};
 	hipStreamCreateWithFlags(&st[0], 1);
@@ -365,23 +228,11 @@ static void walk_two_threads()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	return run_walks(argc, argv, {
 		{"entries", walk_entries},
 		{"thirty_five_frames", walk_thirty_five_frames},
 		{"overlap_region", walk_overlap_region},
 		{"refusals", walk_refusals},
 		{"two_threads", walk_two_threads},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();
-	return g_fail ? 1 : 0;
+	});
 }

@@ -14,178 +14,11 @@
 // calls on planar frames of the same size, through the same library.
 //
 // usage: sp_model_walks [walk ...]     (no argument: all of them)
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <thread>
-#include <vector>
+#define WALKS_SEED 53
+#include "../sanitize/walks.h"
 
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static std::atomic<int> g_fail{0};
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 53;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
-
-// a semi-planar picture, its planes exactly as large as the contract says: (rows - 1) pitches and one row of whole blocks
-struct Pic {
-	int w, h, depth, sy, sz, nblk, stride, uv_stride, crows;
-	std::vector<uint8_t> Y, UV;
-	Pic(int w_, int h_, int depth_, int sy_, int pad = 0) : w(w_), h(h_), depth(depth_), sy(sy_)
-	{
-		sz = depth > 8 ? 2 : 1;
-		nblk = (w + 15) / 16;
-		stride = nblk * 16 + pad;
-		uv_stride = nblk * 16 + pad;
-		crows = (h + sy - 1) / sy;
-		Y.resize(((size_t)(h - 1) * stride + nblk * 16) * sz);
-		UV.resize(((size_t)(crows - 1) * uv_stride + nblk * 16) * sz);
-		for (auto* p : {&Y, &UV})
-			for (auto& b : *p) b = (uint8_t)rnd();
-	}
-};
-
-struct DevPic {
-	uint8_t *Y = nullptr, *UV = nullptr;
-	size_t ny, nc;
-	explicit DevPic(const Pic& f) : ny(f.Y.size()), nc(f.UV.size())
-	{
-		hipMalloc((void**)&Y, ny); hipMalloc((void**)&UV, nc);
-		hipMemcpy(Y, f.Y.data(), ny, 1); hipMemcpy(UV, f.UV.data(), nc, 1);
-	}
-	~DevPic() { hipFree(Y); hipFree(UV); }
-	DevPic(const DevPic&) = delete;
-	bool holds(const Pic& f) const
-	{
-		std::vector<uint8_t> y(ny), c(nc);
-		hipMemcpy(y.data(), Y, ny, 2); hipMemcpy(c.data(), UV, nc, 2);
-		return y == f.Y && c == f.UV;
-	}
-};
-
-struct Pool {
-	std::vector<std::unique_ptr<DevPic>> fr;
-	std::vector<vfgs_hip_sp_frame> list;
-	Pool(const Pic& f, int n)
-	{
-		for (int i = 0; i < n; i++) { fr.emplace_back(new DevPic(f)); list.push_back({fr.back()->Y, fr.back()->UV}); }
-	}
-	bool all_hold(const Pic& f) const
-	{
-		for (const auto& d : fr) if (!d->holds(f)) return false;
-		return true;
-	}
-};
-
-// (callers hold no lock: the walk that calls from several threads programs before it starts them)
-static void program(int depth, int sx, int sy, bool one_pattern, int shift = 5, int legal = 0)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(depth);
-	vfgs_set_chroma_subsampling(sx, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(shift);
-	vfgs_set_legal_range(legal);
-	vfgs_set_seed(4711);
-}
-
-static vfgs_hip_model* capture(void* stream)
-{
-	vfgs_hip_model* m = nullptr;
-	OK(vfgs_hip_model_capture(&m, stream));
-	CHECK(m != nullptr);
-	return m;
-}
-
-// what the stub's kernel does not read: the model's device bytes, all of them (the device pointer is the handle's first member)
-static void touch_model(const vfgs_hip_model* m)
-{
-	int info[8];
-	OK(vfgs_hip_model_info(m, info));
-	const uint8_t* dev;
-	memcpy(&dev, m, sizeof dev);
-	std::vector<uint8_t> b((size_t)info[7]);
-	hipMemcpy(b.data(), dev, b.size(), 2);
-	unsigned x = 0;
-	for (uint8_t v : b) x += v;
-	CHECK(info[7] > 4096 && x != 0);
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
-
-// the registers the contract's loop leaves -- they depend on the seeds and the geometry, not on the model -- through the planar list calls
-// on planar pictures of the same size
-static Regs planar_regs(const Pic& f, int n, const uint32_t* seeds)
-{
-	const size_t cs = (size_t)f.nblk * 16;     // (a planar chroma row pitch of whole 16-byte units at any block count)
-	std::vector<uint8_t*> mem;
-	std::vector<vfgs_hip_frame_ptrs> l;
-	for (int i = 0; i < n; i++)
-	{
-		uint8_t *y, *u, *v;
-		hipMalloc((void**)&y, (size_t)f.h * f.nblk * 16 * f.sz); hipMalloc((void**)&u, f.crows * cs * f.sz); hipMalloc((void**)&v, f.crows * cs * f.sz);
-		mem.insert(mem.end(), {y, u, v});
-		l.push_back({y, u, v});
-	}
-	if (seeds) OK(vfgs_hip_add_grain_frame_list_seeded_dev(l.data(), seeds, n, f.w, f.h, f.nblk * 16, (unsigned)cs, nullptr));
-	else OK(vfgs_hip_add_grain_frame_list_dev(l.data(), n, f.w, f.h, f.nblk * 16, (unsigned)cs, nullptr));
-	hipDeviceSynchronize();
-	for (auto* p : mem) hipFree(p);
-	return Regs();
-}
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	if (n > 2) { s[0] = 0; s[1] = 0x80000000u; }
-	return s;
-}
-
-static unsigned long long launches()
-{
-	vfgs_hip_launch_info li;
-	return vfgs_hip_last_launch_info(&li) == 0 ? li.launches : 0;
-}
+using Pic = SpPic;
+using Pool = SpPool;
 
 static bool spml_named(const vfgs_hip_launch_info& li)
 {
@@ -210,7 +43,7 @@ static void walk_entries()
 		program(depth, 2, sy, c[4] != 0);
 		vfgs_hip_model* b = capture(st);
 		const vfgs_hip_model* ms[5] = {a, b, b, a, b};
-		Pic f(w, h, depth, sy, c[6]);
+		Pic f(w, h, sy, depth > 8 ? 2 : 1, c[6], c[6]);
 		const std::vector<uint32_t> seeds = seeds_of(n);
 		vfgs_set_seed(99);
 		const Regs want_plain = planar_regs(f, n, nullptr);
@@ -252,7 +85,7 @@ static void walk_form_changes()
 	for (const auto& c : cases)
 	{
 		const int w = c[0], h = c[1], depth = c[2], sy = c[3], n = 70, shift = depth > 8 ? 16 - depth : 0;
-		Pic f(w, h, depth, sy);
+		Pic f(w, h, sy, depth > 8 ? 2 : 1);
 		program(depth, 2, sy, false);
 		vfgs_hip_model* g = capture(st);           // general form
 		program(depth, 2, sy, true, 4, 1);
@@ -293,7 +126,7 @@ static void walk_release_while_queued()
 	void *sa = nullptr, *sb = nullptr;
 	hipStreamCreateWithFlags(&sa, 1);
 	hipStreamCreateWithFlags(&sb, 1);
-	Pic f(520, 70, 10, 2);
+	Pic f(520, 70, 2, 2);
 	program(10, 2, 2, true);
 	vfgs_hip_model* a = capture(sa);
 	vfgs_hip_model* a2 = capture(sa);
@@ -346,7 +179,7 @@ static void walk_release_while_queued()
 // two host threads calling on two streams with the same models, a third capturing and releasing
 static void walk_threads()
 {
-	Pic f(520, 70, 10, 2);
+	Pic f(520, 70, 2, 2);
 	program(10, 2, 2, true);
 	vfgs_hip_model* a = capture(nullptr);
 	vfgs_hip_model* b = capture(nullptr);
@@ -395,7 +228,7 @@ static void walk_threads()
 
 static void walk_refusals()
 {
-	Pic f(520, 70, 10, 2);
+	Pic f(520, 70, 2, 2);
 	program(8, 2, 2, true);
 	vfgs_hip_model* m8 = capture(nullptr);
 	program(10, 2, 1, true);
@@ -431,7 +264,7 @@ static void walk_refusals()
 	CHECK(call(L.data(), L.data(), ok, 520, 0, 0, 4) == 40 && strstr(vfgs_hip_last_error_string(), "sample_shift 4"));
 	{
 		// (planes of that width: the list checks, which come first, find nothing)
-		Pic wide(8208, 17, 10, 2);
+		Pic wide(8208, 17, 2, 2);
 		Pool wp(wide, 3);
 		CHECK(vfgs_hip_add_grain_sp_frame_list_models_dev(wp.list.data(), wp.list.data(), ok, seeds.data(), 3, 8208, 17, wide.stride, wide.uv_stride, 6, nullptr) == 40 &&
 		      strstr(vfgs_hip_last_error_string(), "8208"));
@@ -476,23 +309,12 @@ static void walk_refusals()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	// run_walks shuts down with live models (walk_refusals leaves four)
+	return run_walks(argc, argv, {
 		{"entries", walk_entries},
 		{"form_changes", walk_form_changes},
 		{"release_while_queued", walk_release_while_queued},
 		{"threads", walk_threads},
 		{"refusals", walk_refusals},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();         // with live models (walk_refusals leaves four)
-	return g_fail ? 1 : 0;
+	});
 }

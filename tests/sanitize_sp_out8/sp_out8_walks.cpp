@@ -10,87 +10,11 @@
 // suite's business (tests/test_gpu_semiplanar_out8.py).
 //
 // usage: sp_out8_walks [walk ...]     (no argument: all of them)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <vector>
+#define WALKS_SEED 99
+#include "../sanitize/walks.h"
 
-#include "../../include/vfgs_hip.h"
-
-extern "C" int hipMalloc(void** p, size_t n);
-extern "C" int hipFree(void* p);
-extern "C" int hipMemcpy(void* d, const void* s, size_t n, int kind);
-extern "C" int hipStreamCreateWithFlags(void** s, unsigned flags);
-extern "C" int hipStreamDestroy(void* s);
-extern "C" int hipStreamSynchronize(void* s);
-extern "C" int hipDeviceSynchronize(void);
-
-static int g_fail = 0;
-#define CHECK(c)                                                                     \
-	do {                                                                             \
-		if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-	} while (0)
-#define OK(call)                                                                                                    \
-	do {                                                                                                            \
-		const int rc_ = (call);                                                                                     \
-		if (rc_) { fprintf(stderr, "FAILED %s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #call, rc_, vfgs_hip_last_error_string()); g_fail++; } \
-	} while (0)
-
-static uint32_t g_lcg = 99;
-static uint32_t rnd() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
-static uint32_t rnd32() { return rnd() << 8 ^ rnd(); }
-
-// a semi-planar picture of `sz`-byte containers, its planes exactly as large as the contract says: (rows - 1) pitches and one row of whole
-// blocks; pad / uv_pad: containers a row pitch exceeds the whole blocks by
-struct Pic {
-	int w, h, sy, sz, nblk, stride, uv_stride, crows;
-	std::vector<uint8_t> Y, UV;
-	Pic(int w_, int h_, int sy_, int sz_, int pad = 0, int uv_pad = 0) : w(w_), h(h_), sy(sy_), sz(sz_)
-	{
-		nblk = (w + 15) / 16;
-		stride = nblk * 16 + pad;
-		uv_stride = nblk * 16 + uv_pad;
-		crows = (h + sy - 1) / sy;
-		Y.resize(((size_t)(h - 1) * stride + nblk * 16) * sz);
-		UV.resize(((size_t)(crows - 1) * uv_stride + nblk * 16) * sz);
-		for (auto* p : {&Y, &UV})
-			for (auto& b : *p) b = (uint8_t)rnd();
-	}
-};
-
-struct DevPic {
-	uint8_t *Y = nullptr, *UV = nullptr;
-	size_t ny, nc;
-	explicit DevPic(const Pic& f) : ny(f.Y.size()), nc(f.UV.size())
-	{
-		hipMalloc((void**)&Y, ny); hipMalloc((void**)&UV, nc);
-		hipMemcpy(Y, f.Y.data(), ny, 1); hipMemcpy(UV, f.UV.data(), nc, 1);
-	}
-	~DevPic() { hipFree(Y); hipFree(UV); }
-	DevPic(const DevPic&) = delete;
-	bool holds(const Pic& f) const
-	{
-		std::vector<uint8_t> y(ny), c(nc);
-		hipMemcpy(y.data(), Y, ny, 2); hipMemcpy(c.data(), UV, nc, 2);
-		return y == f.Y && c == f.UV;
-	}
-};
-
-struct Pool {
-	std::vector<std::unique_ptr<DevPic>> fr;
-	std::vector<vfgs_hip_sp_frame> list;
-	Pool(const Pic& f, int n)
-	{
-		for (int i = 0; i < n; i++) { fr.emplace_back(new DevPic(f)); list.push_back({fr.back()->Y, fr.back()->UV}); }
-	}
-	bool all_hold(const Pic& f) const
-	{
-		for (const auto& d : fr) if (!d->holds(f)) return false;
-		return true;
-	}
-};
+using Pic = SpPic;
+using Pool = SpPool;
 
 // what the model's launch leaves in a destination that held `fill`: in every row of the picture the whole blocks' bytes are the source's
 // containers narrowed as they lie, (c + 2) >> 2; everything else is the fill's
@@ -103,66 +27,6 @@ static Pic modelled(const Pic& src, const Pic& fill)
 	for (int r = 0; r < src.crows; r++)
 		for (int i = 0; i < src.nblk * 16; i++) out.UV[(size_t)r * fill.uv_stride + i] = (uint8_t)((suv[(size_t)r * src.uv_stride + i] + 2) >> 2);
 	return out;
-}
-
-static void program(int sy, bool one_pattern)
-{
-	vfgs_hip_reset_state();
-	vfgs_set_depth(10);
-	vfgs_set_chroma_subsampling(2, sy);
-	signed char P[4096];
-	for (int k = 0; k < 8; k++)
-	{
-		for (int i = 0; i < 4096; i++) P[i] = (signed char)((int)(rnd() % 255) - 127);
-		vfgs_set_luma_pattern(k, P);
-		vfgs_set_chroma_pattern(k, P);
-	}
-	unsigned char lut[256];
-	for (int c = 0; c < 3; c++)
-	{
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(rnd() % 200);
-		vfgs_set_scale_lut(c, lut);
-		for (int i = 0; i < 256; i++) lut[i] = (unsigned char)(one_pattern ? 0x10 : ((i >> 5) << 4));
-		vfgs_set_pattern_lut(c, lut);
-	}
-	vfgs_set_scale_shift(5);
-	vfgs_set_seed(4711);
-}
-
-static std::vector<uint32_t> seeds_of(int n)
-{
-	std::vector<uint32_t> s(n);
-	for (auto& v : s) v = rnd32();
-	if (n > 2) { s[0] = 0; s[1] = 0x80000000u; }
-	return s;
-}
-
-struct Regs {
-	uint32_t r[4];
-	Regs() { vfgs_hip_get_seed_state(r); }
-	bool operator==(const Regs& o) const { return !memcmp(r, o.r, sizeof r); }
-};
-
-// the registers the contract names: those of the planar _copy8 list (seeded or not) on planar pictures of the same size
-static Regs planar_copy8_regs(const Pic& f, int n, const uint32_t* seeds)
-{
-	const size_t cs = (size_t)f.nblk * 16;     // (planar chroma row pitches of whole 16-byte units at any block count)
-	std::vector<uint8_t*> mem;
-	std::vector<vfgs_hip_frame_ptrs> s, d;
-	for (int i = 0; i < n; i++)
-	{
-		uint8_t* p[6];
-		hipMalloc((void**)&p[0], (size_t)f.h * f.nblk * 16 * 2); hipMalloc((void**)&p[1], f.crows * cs * 2); hipMalloc((void**)&p[2], f.crows * cs * 2);
-		hipMalloc((void**)&p[3], (size_t)f.h * f.nblk * 16); hipMalloc((void**)&p[4], f.crows * cs); hipMalloc((void**)&p[5], f.crows * cs);
-		mem.insert(mem.end(), p, p + 6);
-		s.push_back({p[0], p[1], p[2]});
-		d.push_back({p[3], p[4], p[5]});
-	}
-	if (seeds) OK(vfgs_hip_add_grain_frame_list_seeded_copy8_dev(s.data(), d.data(), seeds, n, f.w, f.h, f.nblk * 16, (unsigned)cs, f.nblk * 16, (unsigned)cs, nullptr));
-	else OK(vfgs_hip_add_grain_frame_list_copy8_dev(s.data(), d.data(), n, f.w, f.h, f.nblk * 16, (unsigned)cs, f.nblk * 16, (unsigned)cs, nullptr));
-	hipDeviceSynchronize();
-	for (auto* p : mem) hipFree(p);
-	return Regs();
 }
 
 static bool sp8_launch(const vfgs_hip_launch_info& li)
@@ -183,13 +47,13 @@ static void walk_out_of_place()
 	for (const auto& c : cases)
 	{
 		const int w = c[0], h = c[1], sy = c[2], shift = c[4], n = 5;
-		program(sy, c[3] != 0);
+		program(10, 2, sy, c[3] != 0);
 		Pic f(w, h, sy, 2, c[5], c[5]), fill(w, h, sy, 1, c[6], c[7]);
 		const Pic want = modelled(f, fill);
 		const std::vector<uint32_t> seeds = seeds_of(n);
 		vfgs_set_seed(99);
-		const Regs want_plain = planar_copy8_regs(f, n, nullptr);
-		const Regs want_seeded = planar_copy8_regs(f, n, seeds.data());
+		const Regs want_plain = planar_regs(f, n, nullptr, PLANAR_LIST_COPY8);
+		const Regs want_seeded = planar_regs(f, n, seeds.data(), PLANAR_LIST_COPY8);
 		Pool src(f, n);
 		vfgs_hip_launch_info a, b;
 		{
@@ -219,11 +83,11 @@ static void walk_out_of_place()
 
 static void walk_thirty_three_frames()
 {
-	program(2, true);
+	program(10, 2, 2, true);
 	Pic f(136, 16, 2, 2), fill(136, 16, 2, 1, 16, 32);
 	const Pic want = modelled(f, fill);
 	const std::vector<uint32_t> seeds = seeds_of(33);
-	const Regs want_seeded = planar_copy8_regs(f, 33, seeds.data());
+	const Regs want_seeded = planar_regs(f, 33, seeds.data(), PLANAR_LIST_COPY8);
 	Pool src(f, 33), dst(fill, 33);
 	vfgs_hip_launch_info a, b;
 	CHECK(vfgs_hip_last_launch_info(&a) == 0);
@@ -231,7 +95,7 @@ static void walk_thirty_three_frames()
 	CHECK(vfgs_hip_last_launch_info(&b) == 0 && b.launches - a.launches == 2 && b.nframes == 1 && sp8_launch(b));
 	CHECK(Regs() == want_seeded);
 	vfgs_set_seed(5);
-	const Regs want_plain = planar_copy8_regs(f, 33, nullptr);
+	const Regs want_plain = planar_regs(f, 33, nullptr, PLANAR_LIST_COPY8);
 	vfgs_set_seed(5);
 	CHECK(vfgs_hip_last_launch_info(&a) == 0);
 	OK(vfgs_hip_add_grain_sp_frame_list_copy8_dev(src.list.data(), dst.list.data(), nullptr, 33, f.w, f.h, f.stride, f.uv_stride, fill.stride, fill.uv_stride, 6, nullptr));
@@ -245,13 +109,13 @@ static void walk_overlap_region()
 {
 	void* st = nullptr;
 	hipStreamCreateWithFlags(&st, 1);
-	program(2, true);
+	program(10, 2, 2, true);
 	Pic f(520, 70, 2, 2), fill(520, 70, 2, 1, 0, 16);
 	const Pic want = modelled(f, fill);
 	const std::vector<uint32_t> sb = seeds_of(3);
 	vfgs_set_seed(3);
-	planar_copy8_regs(f, 4, nullptr);
-	const Regs regs = planar_copy8_regs(f, 3, sb.data());
+	planar_regs(f, 4, nullptr, PLANAR_LIST_COPY8);
+	const Regs regs = planar_regs(f, 3, sb.data(), PLANAR_LIST_COPY8);
 	Pool a(f, 4), b(f, 3), da(fill, 4), db(fill, 3);
 	vfgs_set_seed(3);
 	OK(vfgs_hip_overlap_begin(st));
@@ -267,7 +131,7 @@ static void walk_overlap_region()
 
 static void walk_refusals()
 {
-	program(2, false);
+	program(10, 2, 2, false);
 	Pic f(520, 70, 2, 2), fill(520, 70, 2, 1, 16, 32);
 	Pool pool(f, 3), other(fill, 3);
 	const std::vector<uint32_t> seeds = seeds_of(3);
@@ -332,7 +196,7 @@ static void walk_refusals()
 	hipDeviceSynchronize();
 	CHECK(pool.all_hold(f) && other.all_hold(fill));
 	// the same lists are served afterwards
-	const Regs want = planar_copy8_regs(f, 3, seeds.data());
+	const Regs want = planar_regs(f, 3, seeds.data(), PLANAR_LIST_COPY8);
 	vfgs_set_seed(1);
 	OK(vfgs_hip_add_grain_sp_frame_list_copy8_dev(L.data(), D.data(), seeds.data(), 3, 520, h, s, u, ds, du, 6, nullptr));
 	CHECK(Regs() == want);
@@ -342,22 +206,10 @@ static void walk_refusals()
 
 int main(int argc, char** argv)
 {
-	struct { const char* name; void (*fn)(); } walks[] = {
+	return run_walks(argc, argv, {
 		{"out_of_place", walk_out_of_place},
 		{"thirty_three_frames", walk_thirty_three_frames},
 		{"overlap_region", walk_overlap_region},
 		{"refusals", walk_refusals},
-	};
-	for (const auto& w : walks)
-	{
-		bool want = argc < 2;
-		for (int i = 1; i < argc; i++) want = want || !strcmp(argv[i], w.name);
-		if (!want) continue;
-		const int before = g_fail;
-		w.fn();
-		printf("%-28s %s\n", w.name, g_fail == before ? " ok " : "FAILED");
-		fflush(stdout);
-	}
-	vfgs_hip_shutdown();
-	return g_fail ? 1 : 0;
+	});
 }

@@ -109,19 +109,11 @@ def test_a_call_behind_images_built_ahead_does_not_walk_the_stream_from_bit_0(tm
     from an older one, not from the seed (a few hundred thousand frames into a stream, bit 0 is seconds away).  Host layer over the
     HIP runtime model of tests/sanitize (no GPU): 3,000 chained 64-frame stripe calls at the 8-rank shape of 4320p, then whole frames."""
     import os
-    import shutil
     import subprocess
-    import time
-    from pathlib import Path
-    root = Path(__file__).resolve().parent.parent
-    csrc, inc = root / "versatilefilmgrain_amd" / "csrc", Path(os.environ.get("ROCM_PATH", "/opt/rocm")) / "include"
-    if shutil.which("g++") is None or not (inc / "hip" / "hip_runtime_api.h").exists():
+    import sanitize_build as S
+    if not S.HAVE_TOOLS:
         pytest.skip("needs g++ and the HIP headers")
-    so = tmp_path / "libvfgs_host_model.so"
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", f"-I{inc}", f'-DVFGS_FW_TABLES_PATH="{csrc / "fw_tables.bin"}"',
-                        str(csrc / "vfgs_host.cpp"), str(csrc / "vfgs_fw_host.cpp"), str(csrc / "vfgs_cfg_host.cpp"), str(root / "tests" / "sanitize" / "hip_stub.cpp"),
-                        "-o", str(so), "-pthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    so = S.build(tmp_path, "libvfgs_host_model.so", S.OPTIMISED, [], shared=True)
     code = f"""
 import ctypes as C, time, sys
 lib = C.CDLL({str(so)!r})

@@ -129,15 +129,10 @@ def test_c99_caller_compiles_links_and_runs(tmp_path):
 
 
 def test_host_only_refusals_have_the_documented_codes(tmp_path):
-    from test_sanitize_cpu import CSRC, HIP_INCLUDE, HOST_SOURCES, SAN
-    if shutil.which("gcc") is None or shutil.which("g++") is None or not (HIP_INCLUDE / "hip" / "hip_runtime_api.h").exists():
+    import sanitize_build as S
+    if shutil.which("gcc") is None or not S.HAVE_TOOLS:
         pytest.skip("needs gcc, g++ and the HIP headers")
-    obj = compile_c(tmp_path)
-    exe = tmp_path / "models_out8_refusals"
-    cmd = ["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", f"-I{HIP_INCLUDE}", f'-DVFGS_FW_TABLES_PATH="{CSRC / "fw_tables.bin"}"',
-           *map(str, HOST_SOURCES), str(SAN / "hip_stub.cpp"), str(obj), "-o", str(exe), "-pthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
+    exe = S.build(tmp_path, "models_out8_refusals", S.PLAIN, [compile_c(tmp_path)])
     r = subprocess.run([str(exe), "refusals"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "abi ok" in r.stdout, (r.returncode, r.stdout, r.stderr[-2000:])
 

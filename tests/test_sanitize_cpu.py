@@ -10,76 +10,58 @@ pipelines, replicas on several devices, batches, parts, lists, overlap regions, 
 and never wires it (/root/reference/CMakeLists.txt:25-29).  Values are the GPU suite's business; here the sanitizers check
 addresses, lifetimes and threads, and the walks check that what a call hands back is what the (zero-grain) stub kernel made of it.
 """
-import os
-import shutil
-import subprocess
-from pathlib import Path
-
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "versatilefilmgrain_amd" / "csrc"
-SAN = ROOT / "tests" / "sanitize"
-HOST_SOURCES = [CSRC / "vfgs_host.cpp", CSRC / "vfgs_fw_host.cpp", CSRC / "vfgs_cfg_host.cpp"]
-HIP_INCLUDE = Path(os.environ.get("ROCM_PATH", "/opt/rocm")) / "include"
+import sanitize_build as S
+from sanitize_build import ASAN_UBSAN, CSRC, SAN, STUB, TSAN, build, check_asan_ubsan, check_tsan, needs_gxx, run
 
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None or not (HIP_INCLUDE / "hip" / "hip_runtime_api.h").exists(),
-                                reason="needs g++ and the HIP headers")
+WALKS = SAN / "host_walks.cpp"
+NWALKS = 10
 
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", *flags, "-D__HIP_PLATFORM_AMD__", f"-I{HIP_INCLUDE}",
-           f'-DVFGS_FW_TABLES_PATH="{CSRC / "fw_tables.bin"}"', *map(str, HOST_SOURCES), str(SAN / "hip_stub.cpp"), str(SAN / "host_walks.cpp"),
-           "-o", str(exe), "-pthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
-
-
-def no_aslr_prefix():
-    """GCC's ThreadSanitizer has a fixed memory layout and stops at start-up ("unexpected memory mapping") where the kernel
-    randomises mappings more widely than it expects; it does not re-run itself without randomisation, so the walk is started
-    that way (a personality of that one process) wherever setarch may do so."""
-    cmd = ["setarch", os.uname().machine, "-R"]
-    if shutil.which("setarch") and subprocess.run(cmd + ["true"], capture_output=True).returncode == 0:
-        return cmd
-    return []
-
-
-def run(exe, env_extra, *walks, prefix=()):
-    env = dict(os.environ, **env_extra)
-    for k in ("VFGS_HIP_FRAME_HEIGHT", "VFGS_HIP_LINE_LOOKAHEAD", "LD_PRELOAD"):
-        env.pop(k, None)
-    r = subprocess.run([*prefix, str(exe), *walks], capture_output=True, text=True, env=env, timeout=600)
-    return r
+pytestmark = needs_gxx
 
 
 def test_host_layer_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    exe = build(tmp_path, "walks_asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
-    r = run(exe, {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-6000:])
-    assert r.stdout.count(" ok ") == 10 and "FAILED" not in r.stdout, r.stdout
+    check_asan_ubsan(build(tmp_path, "walks_asan", ASAN_UBSAN, [WALKS]), NWALKS)
 
 
 def test_host_layer_under_thread_sanitizer(tmp_path):
-    exe = build(tmp_path, "walks_tsan", ["-fsanitize=thread"])
-    r = run(exe, {"TSAN_OPTIONS": "halt_on_error=0:second_deadlock_stack=1"}, prefix=no_aslr_prefix())
-    assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-6000:])
-    assert r.stdout.count(" ok ") == 10 and "FAILED" not in r.stdout, r.stdout
+    check_tsan(build(tmp_path, "walks_tsan", TSAN, [WALKS]), NWALKS)
+
+
+def overflow_is_seen(tmp_path, walks, walk, allocator=None):
+    """a stub kernel that walks one row past every plane, built only with -fsanitize=address, under one walk of one program: reported, and
+    (allocator given) the block it ran past is one that this type of tests/sanitize/walks.h allocated"""
+    bad = tmp_path / "hip_stub_bad.cpp"
+    src = STUB.read_text()
+    assert "r < row_first + pd.nrows; r++)" in src
+    bad.write_text(src.replace("r < row_first + pd.nrows; r++)", "r < row_first + pd.nrows + 1; r++)")
+                   .replace('"../../versatilefilmgrain_amd/csrc/', f'"{CSRC}/'))
+    obj = tmp_path / "hip_stub_bad.o"
+    r = S.gxx(("-O1", "-fsanitize=address"), "-c", bad, "-o", obj)
+    assert r.returncode == 0, r.stderr[-4000:]
+    exe = build(tmp_path, "walks_bad", ASAN_UBSAN, [obj, SAN.parent / walks], stub=False)
+    r = run(exe, {}, walk)
+    assert r.returncode != 0 and "heap-buffer-overflow" in r.stderr, r.stderr[-3000:]
+    if allocator:
+        allocated_by = r.stderr.split("allocated by", 1)[1].split("SUMMARY", 1)[0]
+        assert f"{allocator}::{allocator}" in allocated_by, allocated_by[:3000]
 
 
 def test_the_harness_sees_a_kernel_that_touches_one_row_too_many(tmp_path):
     """The check of the checker: the same build with a stub kernel that walks one row past every plane must be reported."""
-    bad = tmp_path / "hip_stub_bad.cpp"
-    src = (SAN / "hip_stub.cpp").read_text()
-    assert "r < row_first + pd.nrows; r++)" in src
-    bad.write_text(src.replace("r < row_first + pd.nrows; r++)", "r < row_first + pd.nrows + 1; r++)")
-                   .replace('"../../versatilefilmgrain_amd/csrc/', f'"{CSRC}/'))
-    exe = tmp_path / "walks_bad"
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address", "-D__HIP_PLATFORM_AMD__", f"-I{HIP_INCLUDE}",
-           f'-DVFGS_FW_TABLES_PATH="{CSRC / "fw_tables.bin"}"', *map(str, HOST_SOURCES), str(bad), str(SAN / "host_walks.cpp"), "-o", str(exe), "-pthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = run(exe, {}, "device_entries")
-    assert r.returncode != 0 and "heap-buffer-overflow" in r.stderr, r.stderr[-3000:]
+    overflow_is_seen(tmp_path, "sanitize/host_walks.cpp", "device_entries")
+
+
+@pytest.mark.parametrize("walks,walk,allocator", [("sanitize/picture_walks.cpp", "sp_pool", "DevSpPic"), ("sanitize_seeded/seeded_walks.cpp", "entries", "DevFrame")],
+                         ids=["picture_walks", "seeded_walks"])
+def test_the_harness_sees_a_kernel_that_touches_one_row_too_many_in_the_shared_pictures(tmp_path, walks, walk, allocator):
+    """... and so through the picture types of tests/sanitize/walks.h, on which "exactly as large as the contract says" rests for every other
+    program: the block the kernel ran past was allocated by the shared semi-planar picture's device copy (tests/sanitize/picture_walks.cpp,
+    whose first launch runs on an SpPool; the walks of sp_walks.cpp all launch on planar_regs()' scratch planes first, where the sanitizer
+    would stop), and by the shared planar device frame (the first launch of seeded_walks' `entries`)."""
+    overflow_is_seen(tmp_path, walks, walk, allocator)
+
+
+def test_the_picture_walk_is_clean_over_the_unchanged_stub(tmp_path):
+    check_asan_ubsan(build(tmp_path, "picture_walks_asan", ASAN_UBSAN, [SAN / "picture_walks.cpp"]), 1)

@@ -1,41 +1,20 @@
 """CPU: the frame lists with a seed per picture in the host layer under AddressSanitizer + UndefinedBehaviorSanitizer and under
-ThreadSanitizer: tests/sanitize_seeded/seeded_walks.cpp, built the way tests/test_sanitize_depth12_cpu.py builds its walks, against the
+ThreadSanitizer: tests/sanitize_seeded/seeded_walks.cpp, built by tests/sanitize_build.py, against the
 unchanged model of the HIP runtime tests/sanitize/hip_stub.cpp (host code on the CPU only; that model aborts when a launch addresses
 LFSR bits behind the image it was handed, and its deferred queues run a launch long after the call that queued it -- a slot of the
 images' ring that is overwritten or freed too early is an access the sanitizer sees).  Values are the GPU suite's business
 (tests/test_gpu_seeded_list.py)."""
-import shutil
-import subprocess
-
-import pytest
-
-from test_sanitize_cpu import CSRC, HIP_INCLUDE, HOST_SOURCES, SAN, no_aslr_prefix, run
+from sanitize_build import ASAN_UBSAN, SAN, TSAN, build, check_asan_ubsan, check_tsan, needs_gxx
 
 WALKS = SAN.parent / "sanitize_seeded" / "seeded_walks.cpp"
 NWALKS = 7
 
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None or not (HIP_INCLUDE / "hip" / "hip_runtime_api.h").exists(),
-                                reason="needs g++ and the HIP headers")
-
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", *flags, "-D__HIP_PLATFORM_AMD__", f"-I{HIP_INCLUDE}",
-           f'-DVFGS_FW_TABLES_PATH="{CSRC / "fw_tables.bin"}"', *map(str, HOST_SOURCES), str(SAN / "hip_stub.cpp"), str(WALKS), "-o", str(exe), "-pthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+pytestmark = needs_gxx
 
 
 def test_seeded_walks_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    exe = build(tmp_path, "seeded_walks_asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
-    r = run(exe, {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
-    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-6000:])
-    assert r.stdout.count(" ok ") == NWALKS and "FAILED" not in r.stdout, r.stdout
+    check_asan_ubsan(build(tmp_path, "seeded_walks_asan", ASAN_UBSAN, [WALKS]), NWALKS)
 
 
 def test_seeded_walks_under_thread_sanitizer(tmp_path):
-    exe = build(tmp_path, "seeded_walks_tsan", ["-fsanitize=thread"])
-    r = run(exe, {"TSAN_OPTIONS": "halt_on_error=0:second_deadlock_stack=1"}, prefix=no_aslr_prefix())
-    assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-6000:])
-    assert r.stdout.count(" ok ") == NWALKS and "FAILED" not in r.stdout, r.stdout
+    check_tsan(build(tmp_path, "seeded_walks_tsan", TSAN, [WALKS]), NWALKS)

@@ -5,12 +5,9 @@ is the stream of the register seeds[f] << 1 (vfgs_hw.c:339-344) from first_bit o
 tests/test_lfsr_jump_cpu.py), and -- the seed registers the entry points leave -- through the host layer over the HIP runtime model of
 tests/sanitize (no GPU) against the oracle run as the contract's loop: set_seed(seeds[f]); add_grain_frame(frame f)."""
 import ctypes as C
-import os
-import shutil
 import subprocess
 import sys
 import time
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -163,15 +160,10 @@ def test_seed_registers_of_the_entry_points_over_the_runtime_model(tmp_path):
     """seeded lists of 200 x 150 (whole, a part, 70 frames = three launches, out of place), refused calls in between, unseeded calls that
     continue the last picture's stream: vfgs_hip_get_seed_state against the oracle's after the contract's loop, every time"""
     import json
-    root = Path(__file__).resolve().parent.parent
-    csrc, inc = root / "versatilefilmgrain_amd" / "csrc", Path(os.environ.get("ROCM_PATH", "/opt/rocm")) / "include"
-    if shutil.which("g++") is None or not (inc / "hip" / "hip_runtime_api.h").exists():
+    import sanitize_build as S
+    if not S.HAVE_TOOLS:
         pytest.skip("needs g++ and the HIP headers")
-    so = tmp_path / "libvfgs_host_model.so"
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", f"-I{inc}", f'-DVFGS_FW_TABLES_PATH="{csrc / "fw_tables.bin"}"',
-                        str(csrc / "vfgs_host.cpp"), str(csrc / "vfgs_fw_host.cpp"), str(csrc / "vfgs_cfg_host.cpp"), str(root / "tests" / "sanitize" / "hip_stub.cpp"),
-                        "-o", str(so), "-pthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    so = S.build(tmp_path, "libvfgs_host_model.so", S.OPTIMISED, [], shared=True)
     r = subprocess.run([sys.executable, "-c", MODEL_DRIVER, str(so)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     log = json.loads(r.stdout.split("LOG", 1)[1])
