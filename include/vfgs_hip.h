@@ -432,8 +432,9 @@ void vfgs_hip_get_model_build_stats(uint64_t out[8]);
  * (rows walked in parts); an active PROGRAMMED chroma mix ("chroma mix" in the message: a mix reaches this call in its models).  A model
  * that carries a mix adds no refusal of its own: depth and form were checked where the mix was attached.  An empty list is no call at all.
  * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination under a mix (without one:
- * vfgs_hip_add_grain_frame_list_models_copy8_dev below), stripe / part forms, host-memory entry points, widths above 8192, persistent
- * luma workgroups (1080p general-form luma runs without them here).  Semi-planar surfaces have the call below. */
+ * vfgs_hip_add_grain_frame_list_models_copy8_dev below), stripe / part forms, widths above 8192, persistent luma workgroups (1080p
+ * general-form luma runs without them here).  Semi-planar surfaces have the call below; pictures in host memory have
+ * vfgs_hip_host_pipe_submit, where semi-planar host surfaces and several devices are still out. */
 int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
                                              const vfgs_hip_model* const* models,     /* nframes entries */
                                              const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
@@ -463,8 +464,8 @@ int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, con
  * programmed one, an active PROGRAMMED chroma mix ("chroma mix" in the message).  Where several apply: the list checks, then 40, then 41.
  * An empty list is no call at all.
  * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination under a mix (without one:
- * vfgs_hip_add_grain_sp_frame_list_models_copy8_dev below), a planar source, stripe / part forms, host-memory entry points, 4:4:4,
- * widths above 8192. */
+ * vfgs_hip_add_grain_sp_frame_list_models_copy8_dev below), a planar source, stripe / part forms, semi-planar surfaces in host memory
+ * (vfgs_hip_host_pipe_submit takes planar pictures), several devices, 4:4:4, widths above 8192. */
 int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                                 const vfgs_hip_model* const* models,   /* nframes entries, host memory */
                                                 const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
@@ -501,8 +502,8 @@ int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, co
  * the cause: models == NULL, a NULL or released entry, a model of another depth or chroma format than the programmed one, width > 8192, an
  * active PROGRAMMED chroma mix, a model in the list that CARRIES a mix ("chroma mix" in both messages: the kernels of the mix have no
  * narrowed form with a model per frame).  An empty list is no call at all.
- * Out of scope, on purpose: models that carry a mix, widths above 8192, stripe / part forms, host-memory entry points, persistent luma
- * workgroups. */
+ * Out of scope, on purpose: models that carry a mix, widths above 8192, stripe / part forms, persistent luma workgroups.  Pictures in host
+ * memory have vfgs_hip_host_pipe_submit (dst8), where semi-planar host surfaces and several devices are still out. */
 int vfgs_hip_add_grain_frame_list_models_copy8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
                                                    const vfgs_hip_model* const* models,     /* nframes entries, host memory */
                                                    const uint32_t* seeds,      /* NULL: one seed sequence; else a seed per picture */
@@ -528,7 +529,7 @@ int vfgs_hip_add_grain_frame_list_models_copy8_dev(const vfgs_hip_frame_ptrs* sr
  * dst_uv_stride), then depth 8: 16, then 40 (csubx != 2, a bad sample_shift, width > 8192), then 41 as above (width aside, which is 40
  * here).  An empty list is no call at all.
  * Out of scope, on purpose: models that carry a mix, a planar source (the _to_sp8 call has no form with models), 4:4:4, widths above
- * 8192, stripe / part forms, host-memory entry points. */
+ * 8192, stripe / part forms, semi-planar surfaces in host memory (vfgs_hip_host_pipe_submit takes planar pictures), several devices. */
 int vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                                       const vfgs_hip_model* const* models,   /* nframes entries, host memory */
                                                       const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
@@ -625,6 +626,65 @@ int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* 
                                    unsigned height, unsigned stride, unsigned cstride);
 void* vfgs_hip_host_alloc(uint64_t bytes);   /* pinned host memory (hipHostMalloc); NULL on failure */
 void vfgs_hip_host_free(void* p);
+
+/* PICTURES IN HOST MEMORY AS A STREAM: what a software decoder (dav1d, vvdec, VTM, libde265) hands out -- planar pictures in host memory,
+ * one at a time, each with its own grain_seed and usually its own parameter set -- through the pipeline of the call above, fed picture by
+ * picture.  A pipe is opened for one geometry at the programmed depth and chroma format; vfgs_hip_host_pipe_submit queues upload, launch and
+ * download of ONE picture on the library's three pipeline streams and returns a ticket; vfgs_hip_host_pipe_wait(ticket) returns when that
+ * picture and every earlier one of the pipe are in host memory.
+ * desc: width / height / stride / cstride as in vfgs_hip_add_grain_frames_host (strides in samples).  dst_stride = dst_cstride = 0: every
+ * picture is grained in place.  Else every picture has a destination of its own in host memory, rows of dst_stride / dst_cstride
+ * destination samples: samples of the source's size, or with dst8 = 1 (depth 10 or 12) bytes, narrowed in the store as in the _copy8 calls.
+ * slots: pictures in flight, 0 = 3, else 2..8; a slot holds a device source and, with a destination, a device destination, at pitches of
+ * the library's choosing.
+ * WHAT A SUBMIT COMPUTES.  After wait(ticket) returned 0 the destination bytes, the bytes left alone and the source are what the matching
+ * one-picture device call gives, had the planes been device memory at the moment of the submit:
+ *     model, no dst8                        vfgs_hip_add_grain_frame_list_models_dev(&s, &d, &model, seed, 1, ...)
+ *     model, dst8                           vfgs_hip_add_grain_frame_list_models_copy8_dev
+ *     model == NULL, seed == NULL           vfgs_hip_add_grain_frame_list_copy_dev        dst8: ..._copy8_dev
+ *     model == NULL, a seed                 vfgs_hip_add_grain_frame_list_seeded_copy_dev dst8: ..._seeded_copy8_dev
+ * (model == NULL: the programmed state as it is at the submit; seed == NULL: the running seed sequence; *seed is read during the call.)
+ * Only whole 16-sample blocks of every row travel: stride padding is never written, and a source with a destination of its own is never
+ * written at all.  A model that carries a mix is honoured as in the device call.  THE FOUR SEED REGISTERS move at the submit, on the host,
+ * exactly as that device call moves them -- vfgs_hip_get_seed_state right behind a submit is the device call's -- so submits interleave
+ * with every other entry point in one seed sequence.  The programmed state is left alone, as by the calls with models.
+ * HOST MEMORY: source and destination planes stay valid and untouched until the picture's wait returns; the model may be released as soon
+ * as submit returns.  Pinned memory (vfgs_hip_host_alloc) makes the copies asynchronous; pageable memory is correct and blocks the caller
+ * in submit, as in the call above.  A submit that finds every slot in flight waits on the host for the pipe's oldest picture
+ * (back-pressure; no error).
+ * TICKETS count 1, 2, 3 ... per pipe; a wait on a ticket that is home returns 0 again.  THREADS: one thread may submit while another
+ * waits on the same pipe -- wait does not hold the library's lock while it sleeps --; several pipes, of different geometry, may be open at
+ * once (their pictures share the three streams: all of them come home in the order of their submits).  close drains the pipe and frees
+ * its ring; vfgs_hip_shutdown drains and closes whatever is open, and every handle is stale behind it.
+ * vfgs_hip_last_launch_info(): internal = 1, listed = 1, and the kernel the matching device call records.
+ * REFUSED with nothing queued, no ticket issued, no register moved and the pipe usable as before: everything the matching device call
+ * refuses, with that call's code and text behind the name of the pipe's function -- 5 / 6 / 8 / 17 and 15 for the geometry (the caller's
+ * strides) and 16 for dst8 at depth 8, all at open; at submit 18 (a null plane; a destination plane that shares bytes with another one or
+ * with a plane of the source), 41 (the model: NULL entry aside, released, another depth or format, width > 8192, a programmed mix beside
+ * a model, a model that carries a mix with dst8), 38, 9 and 4 (the programmed state of a submit without a model).  Error 43, the pipe's
+ * own, with the cause in the message: a null desc, out, p, src or ticket; a closed or unknown handle (never dereferenced); slots outside
+ * 2..8; dst8 with zero destination strides; pictures without lines; a dst on a pipe opened in place, or none on one opened with
+ * destination strides; a wait on a ticket never issued; a submit after the programmed depth or chroma format changed since open; a submit
+ * while an overlap region is open; open or submit with more than one device of vfgs_hip_init_devices.  A HIP error in mid-stream drains
+ * the three streams before it is returned.
+ * Out of scope, on purpose: semi-planar host surfaces, a semi-planar destination, several devices, polling without waiting. */
+typedef struct vfgs_hip_host_pipe vfgs_hip_host_pipe;          /* opaque */
+typedef struct vfgs_hip_host_pipe_desc {
+	unsigned width, height;            /* luma samples, every picture of the pipe */
+	unsigned stride, cstride;          /* source rows in samples, as vfgs_hip_add_grain_frames_host */
+	unsigned dst_stride, dst_cstride;  /* destination rows in destination samples (bytes with dst8); 0, 0: every picture in place */
+	int      dst8;                     /* 1: planar 8-bit destination, narrowed in the store (depth 10 / 12) */
+	unsigned slots;                    /* pictures in flight: 0 = 3, else 2..8 */
+} vfgs_hip_host_pipe_desc;
+int vfgs_hip_host_pipe_open(const vfgs_hip_host_pipe_desc* desc, vfgs_hip_host_pipe** out);
+int vfgs_hip_host_pipe_submit(vfgs_hip_host_pipe* p,
+                              const vfgs_hip_frame_ptrs* src,    /* HOST planes, line 0 */
+                              const vfgs_hip_frame_ptrs* dst,    /* NULL: in place; else HOST planes */
+                              const vfgs_hip_model* model,       /* NULL: the programmed state as it is now */
+                              const uint32_t* seed,              /* NULL: the running seed sequence */
+                              uint64_t* ticket);
+int vfgs_hip_host_pipe_wait(vfgs_hip_host_pipe* p, uint64_t ticket);   /* this picture and every earlier one are in host memory */
+int vfgs_hip_host_pipe_close(vfgs_hip_host_pipe* p);                   /* drains, frees the ring */
 
 /* Introspection for benchmarks/tests. */
 int vfgs_hip_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, char* name, int name_len);

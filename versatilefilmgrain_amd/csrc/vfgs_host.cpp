@@ -17,6 +17,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -1024,6 +1026,13 @@ State& S()
 }
 
 std::mutex g_mu;
+
+// Host-memory pipes (vfgs_hip_host_pipe_*, behind vfgs_hip_add_grain_frames_host below): vfgs_hip_host_pipe_wait sleeps WITHOUT g_mu, so that
+// another thread can submit meanwhile; whoever is about to take away what a sleeper holds -- a slot's events (submit), the pipe (close), the
+// device (vfgs_hip_shutdown) -- waits here, with g_mu, until the sleepers it cares about are back.
+std::condition_variable g_pipe_cv;
+unsigned g_pipe_sleepers = 0;                   // threads inside a pipe's wait, of all pipes together
+void (*g_pipes_release)() = nullptr;            // registered by the first open: frees every open pipe (release_state_impl; the device is idle)
 
 vfgs_hip_launch_info g_last_launch{};      // what the primary state's most recent grain launch dispatched
 bool g_last_launch_valid = false;
@@ -2117,6 +2126,33 @@ int run_host(void* Y, void* U, void* V, unsigned y, unsigned width, unsigned hei
 // With pinned host memory (vfgs_hip_host_alloc) the copies are asynchronous; pageable memory works, the runtime then
 // stages every copy itself and the calling thread blocks for it.  The seed registers advance frame by frame exactly as
 // with nframes calls of the frame entry point.
+// the three streams, one per stage, and the events of the ring above: made by whichever host-memory pipeline comes first -- this call, or a
+// pipe of vfgs_hip_host_pipe_open, whose pictures travel on the same three streams through slots of their own -- and kept until shutdown
+// (the images' SlotGuards remember the streams that read them)
+int host_pipe_streams(State::HostPipe& P)
+{
+	if (P.up) return 0;
+	HIP_TRY(hipStreamCreateWithFlags(&P.up, hipStreamNonBlocking));
+	HIP_TRY(hipStreamCreateWithFlags(&P.run, hipStreamNonBlocking));
+	HIP_TRY(hipStreamCreateWithFlags(&P.down, hipStreamNonBlocking));
+	for (int k = 0; k < State::HostPipe::kDepth; k++)
+	{
+		HIP_TRY(hipEventCreateWithFlags(&P.up_done[k], hipEventDisableTiming));
+		HIP_TRY(hipEventCreateWithFlags(&P.run_done[k], hipEventDisableTiming));
+		HIP_TRY(hipEventCreateWithFlags(&P.down_done[k], hipEventDisableTiming));
+	}
+	return 0;
+}
+
+// the whole blocks of every row of three planes between host and device memory, queued on `stream`; the first error, if any
+hipError_t copy_planes(void* const (&dst)[3], const size_t (&dpitch)[3], const void* const (&src)[3], const size_t (&spitch)[3],
+                       const unsigned (&rowlen)[3], const unsigned (&rows)[3], hipMemcpyKind kind, hipStream_t stream)
+{
+	for (int i = 0; i < 3; i++)
+		if (hipError_t e = hipMemcpy2DAsync(dst[i], dpitch[i], src[i], spitch[i], rowlen[i], rows[i], kind, stream)) return e;
+	return hipSuccess;
+}
+
 // (py, ph: the lines of every frame THIS state's device processes -- the whole frame unless several devices share the frames)
 int run_host_frames(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width, unsigned height,
                     unsigned stride, unsigned cstride, unsigned py, unsigned ph)
@@ -2145,18 +2181,7 @@ int run_host_frames(void* const* Y, void* const* U, void* const* V, unsigned nfr
 		return fail(6, "stride too small: every row must hold whole 16-sample blocks (vfgs_hw.c:301)");
 	const unsigned dpitch[3] = {(rowlen[0] + 255) & ~255u, (rowlen[1] + 255) & ~255u, (rowlen[2] + 255) & ~255u};
 	const size_t spitch[3] = {(size_t)stride * sz, (size_t)cstride * sz, (size_t)cstride * sz};
-	if (!P.up)
-	{
-		HIP_TRY(hipStreamCreateWithFlags(&P.up, hipStreamNonBlocking));
-		HIP_TRY(hipStreamCreateWithFlags(&P.run, hipStreamNonBlocking));
-		HIP_TRY(hipStreamCreateWithFlags(&P.down, hipStreamNonBlocking));
-		for (int k = 0; k < D; k++)
-		{
-			HIP_TRY(hipEventCreateWithFlags(&P.up_done[k], hipEventDisableTiming));
-			HIP_TRY(hipEventCreateWithFlags(&P.run_done[k], hipEventDisableTiming));
-			HIP_TRY(hipEventCreateWithFlags(&P.down_done[k], hipEventDisableTiming));
-		}
-	}
+	if (int e = host_pipe_streams(P)) return e;
 	int rc = 0;
 	// (no early return below: whatever happens, the three streams are drained before the call returns -- copies into the
 	// caller's memory may be in flight)
@@ -2932,6 +2957,7 @@ void release_state_impl(State& s)
 	(void)fw_flush(s, s.own_stream);
 	(void)hipDeviceSynchronize();
 	if (&s == &g_states[0]) release_models();     // (captured models are the primary device's: vfgs_hip_shutdown releases what the caller has not)
+	if (&s == &g_states[0] && g_pipes_release) g_pipes_release();     // (... and so are the pipes: every picture is home, their handles are stale from here on)
 	// device-generated patterns move to the host mirror so the programmed state survives
 	for (int c = 0; c < 2; c++)
 		for (int k = 0; k < vfgs::kSlots; k++)
@@ -3276,7 +3302,8 @@ int vfgs_hip_init_devices(const int* devices, int n)
 
 void vfgs_hip_shutdown(void)
 {
-	std::lock_guard<std::mutex> g(g_mu);
+	std::unique_lock<std::mutex> g(g_mu);
+	g_pipe_cv.wait(g, [] { return g_pipe_sleepers == 0; });     // (threads asleep in vfgs_hip_host_pipe_wait hold events of pipes this call frees)
 	for (int i = kMaxDevices - 1; i >= 0; i--)
 	{
 		if (!g_states[i].inited) continue;
@@ -3440,7 +3467,9 @@ static int check_models_window(const ListCall& l)
 	return 0;
 }
 
-static int launch_list(ListCall& l)
+// admit_only: nothing is queued and nothing moves -- only what would refuse the launches is looked at (Launch::admit), for a caller that has
+// work of its own to queue in front of them (a pipe's upload)
+static int launch_list(ListCall& l, const bool admit_only = false)
 {
 	const vfgs_hip_frame_ptrs *src = l.src, *dst = l.dst;
 	const vfgs_hip_model* const* models = l.models;
@@ -3467,7 +3496,7 @@ static int launch_list(ListCall& l)
 			for (unsigned k = 0; k < n; k++)
 			{
 				vfgs_hip_model* m = const_cast<vfgs_hip_model*>(models[f0 + k]);
-				HIP_TRY(model_guard(m).use(c.stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
+				if (!admit_only) HIP_TRY(model_guard(m).use(c.stream));     // (a first use on another stream than the capture's waits for the upload there; the model remembers its readers)
 				ft.model[k] = m->dev;
 			}
 			mr.one_y = models[f0]->one_y; mr.one_c = models[f0]->one_c;
@@ -3479,6 +3508,7 @@ static int launch_list(ListCall& l)
 		c.nframes = n;
 		c.list = &ft;
 		c.seeds = seeds ? seeds + f0 : nullptr;
+		if (admit_only) { if (int e = Launch(S(), c).admit()) return e; continue; }
 		if (int e = run_device(c)) return e;
 	}
 	return 0;
@@ -3976,6 +4006,291 @@ int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* 
 	S().gen++;
 	S().la.valid = false;
 	return run_host_frames_multi(Y, U, V, nframes, width, height, stride, cstride);
+}
+
+// ------------------------------------------------------------------------------------
+// Pictures in host memory as a STREAM (vfgs_hip.h: vfgs_hip_host_pipe_*): the pipeline of run_host_frames, fed picture by picture.  Every
+// picture brings its own model and seed, may leave through a narrowed 8-bit destination, and is collected later by its ticket.  A pipe owns a
+// ring of slots -- a device source per picture and, with a destination, a device destination -- and nothing else: its pictures travel on the
+// three streams of State::HostPipe (upload, launch, download; shared with vfgs_hip_add_grain_frames_host and with every other pipe, so the
+// downloads of ALL pipes complete in the order of their submits), and the launch of a picture is the list call the header names, made on
+// the slot's device planes by the code of that call.
+} // extern "C"
+
+struct vfgs_hip_host_pipe {
+	vfgs_hip_host_pipe_desc d{};
+	int bs = 0, csubx = 2, csuby = 2;         // the programmed depth and chroma format at open: a submit under another one is refused
+	bool has_dst = false;                     // opened with destination strides: every picture has a destination of its own
+	unsigned nslots = 3, sz = 1;
+	unsigned rows[3] = {}, rowlen[3] = {}, drowlen[3] = {};       // per plane: rows; bytes of a row's whole blocks in the source, in the destination
+	size_t spitch[3] = {}, hpitch[3] = {};    // the caller's row pitches in bytes: source planes, the planes the picture comes home to
+	size_t dpitch[3] = {}, ddpitch[3] = {};   // the slots' row pitches in bytes: device source, the device planes that are downloaded
+	struct Slot {
+		void *src[3] = {}, *dst[3] = {};      // (dst: the device destination, or src again)
+		hipEvent_t up_done = nullptr, run_done = nullptr, down_done = nullptr;
+		uint64_t ticket = 0;                  // the picture the slot held last
+		unsigned sleepers = 0;                // threads asleep on down_done (vfgs_hip_host_pipe_wait): it is not recorded again under them
+	} slot[8];
+	uint64_t issued = 0, home = 0;            // tickets handed out; the newest one known to be in host memory (they come home in order)
+	unsigned sleepers = 0;
+};
+
+namespace {
+std::vector<vfgs_hip_host_pipe*> g_pipes;     // open pipes (a handle that is not in here is refused and never dereferenced)
+
+bool pipe_live(const vfgs_hip_host_pipe* p) { return p && std::find(g_pipes.begin(), g_pipes.end(), p) != g_pipes.end(); }
+
+void pipe_free(vfgs_hip_host_pipe* p)         // (nothing of it is in flight, nobody sleeps on its events)
+{
+	for (vfgs_hip_host_pipe::Slot& sl : p->slot)
+	{
+		for (int i = 0; i < 3; i++)
+		{
+			if (sl.dst[i] && sl.dst[i] != sl.src[i]) (void)hipFree(sl.dst[i]);
+			if (sl.src[i]) (void)hipFree(sl.src[i]);
+		}
+		for (hipEvent_t ev : {sl.up_done, sl.run_done, sl.down_done}) if (ev) (void)hipEventDestroy(ev);
+	}
+	delete p;
+}
+
+void pipes_release()                          // g_pipes_release: vfgs_hip_shutdown, the device is idle
+{
+	for (vfgs_hip_host_pipe* p : g_pipes) pipe_free(p);
+	g_pipes.clear();
+}
+
+// a refusal of the matching device call, as the pipe reports it: that call's code and text behind the pipe's name
+int pipe_passes(const char* who, int code)
+{
+	const std::string text = g_errstr;
+	return fail(code, "%s: %s", who, text.c_str());
+}
+
+// everything the pipe's pictures have queued, home: after a HIP error in mid-stream, and before a pipe is freed
+void pipe_drain(State& s, vfgs_hip_host_pipe* p)
+{
+	if (s.pipe.up) (void)hipStreamSynchronize(s.pipe.up);
+	if (s.pipe.run) (void)hipStreamSynchronize(s.pipe.run);
+	if (s.pipe.down) (void)hipStreamSynchronize(s.pipe.down);
+	p->home = p->issued;
+}
+}  // namespace
+
+// One picture of a pipe as the device call of the header's table sees it, on device planes `s` / `d` (the same list: in place): that call's
+// checks in that call's order, then its launches on the pipe's launch stream -- or, admit_only, everything that would refuse them and nothing else.
+static int pipe_device_call(const vfgs_hip_host_pipe* p, const vfgs_hip_frame_ptrs* s, const vfgs_hip_frame_ptrs* d, const vfgs_hip_model* model,
+                            const uint32_t* seed, const bool admit_only)
+{
+	State& st = S();
+	GrainCall g = GrainCall().rows(p->d.width, (unsigned)(p->dpitch[0] / p->sz), (unsigned)(p->dpitch[1] / p->sz)).whole(p->d.height);
+	if (p->d.dst8) g.dst_rows(true, (unsigned)p->ddpitch[0], (unsigned)p->ddpitch[1]);
+	ListCall l(s, d, 1, seed, st.pipe.run, g);
+	if (!model)
+	{
+		if (int e = check_list(l)) return e;
+		return launch_list(l, admit_only);
+	}
+	const vfgs_hip_model* const models[1] = {model};
+	l.with(models);
+	if (!p->d.dst8)
+	{
+		if (int e = check_models("frame list with models", st, models, 1, p->d.width)) return e;
+		if (int e = check_list(l)) return e;
+		if (int e = check_models_window(l)) return e;
+	}
+	else
+	{
+		const char* const who = "frame list with models, 8-bit destination";
+		if (int e = check_list(l)) return e;
+		if (int e = check_models_window(l)) return e;
+		if (int e = check_out8_rows(st, p->d.width, (unsigned)p->ddpitch[0], (unsigned)p->ddpitch[1], false)) return e;
+		if (int e = check_models(who, st, models, 1, p->d.width)) return e;
+		if (int e = check_models_without_mix(who, models, 1)) return e;
+	}
+	return launch_list(l, admit_only);
+}
+
+extern "C" {
+
+int vfgs_hip_host_pipe_open(const vfgs_hip_host_pipe_desc* desc, vfgs_hip_host_pipe** out)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	const char* const who = "vfgs_hip_host_pipe_open";
+	if (out) *out = nullptr;
+	if (!desc || !out) return fail(43, "%s: null %s", who, desc ? "result pointer" : "description");
+	const vfgs_hip_host_pipe_desc& d = *desc;
+	if (d.slots != 0 && (d.slots < 2 || d.slots > 8)) return fail(43, "%s: %u slots (0 = 3, else 2..8)", who, d.slots);
+	if ((d.dst_stride == 0) != (d.dst_cstride == 0)) return fail(43, "%s: destination strides %u/%u (both, or 0, 0: every picture in place)", who, d.dst_stride, d.dst_cstride);
+	if (d.dst8 && d.dst_stride == 0) return fail(43, "%s: an 8-bit destination is never in place: it needs destination strides", who);
+	if (d.height == 0) return fail(43, "%s: pictures without lines", who);
+	if (g_ndev > 1) return fail(43, "%s: %d devices are set (vfgs_hip_init_devices); a pipe runs on one", who, g_ndev);
+	if (int e = ensure_init(-1)) return e;
+	State& s = g_states[0];
+	// what the matching device calls refuse for a geometry, with their codes: it is the pipe's for as long as it is open
+	if (int e = check_geometry(s, nullptr, nullptr, nullptr, d.width, d.stride, d.cstride, false)) return pipe_passes(who, e);
+	if (d.dst8) { if (int e = check_out8_rows(s, d.width, d.dst_stride, d.dst_cstride, false)) return pipe_passes(who, e); }
+	else if (d.dst_stride) { if (int e = check_geometry(s, nullptr, nullptr, nullptr, d.width, d.dst_stride, d.dst_cstride, false)) return pipe_passes(who, e); }
+
+	std::unique_ptr<vfgs_hip_host_pipe> p(new vfgs_hip_host_pipe);
+	p->d = d;
+	p->bs = s.bs; p->csubx = s.csubx; p->csuby = s.csuby;
+	p->has_dst = d.dst_stride != 0;
+	p->nslots = d.slots ? d.slots : 3;
+	p->sz = s.bs ? 2 : 1;
+	const unsigned nblk = (d.width + 15) / 16, crows = (d.height - 1) / s.csuby + 1, dsz = d.dst8 ? 1 : p->sz;
+	for (int i = 0; i < 3; i++)
+	{
+		const unsigned row = i ? nblk * 16 / s.csubx : nblk * 16;     // samples of a row's whole blocks
+		p->rows[i] = i ? crows : d.height;
+		p->rowlen[i] = row * p->sz; p->drowlen[i] = row * dsz;
+		p->spitch[i] = (size_t)(i ? d.cstride : d.stride) * p->sz;
+		p->hpitch[i] = p->has_dst ? (size_t)(i ? d.dst_cstride : d.dst_stride) * dsz : p->spitch[i];
+		p->dpitch[i] = (p->rowlen[i] + 255) & ~255u;     // (the pitches of run_host_frames' ring)
+		p->ddpitch[i] = (p->drowlen[i] + 255) & ~255u;
+		const uint64_t far = std::max({(uint64_t)p->rows[i] * p->spitch[i], (uint64_t)p->rows[i] * p->hpitch[i], (uint64_t)p->rows[i] * p->dpitch[i]});
+		if (far >= 0x80000000ull) return fail(15, "%s: a plane of %llu bytes exceeds the 2 GiB buffer window", who, (unsigned long long)far);
+	}
+	if (int e = host_pipe_streams(s.pipe)) return e;
+	hipError_t err = hipSuccess;
+	for (unsigned k = 0; k < p->nslots && err == hipSuccess; k++)
+	{
+		vfgs_hip_host_pipe::Slot& sl = p->slot[k];
+		for (int i = 0; i < 3 && err == hipSuccess; i++)
+		{
+			err = hipMalloc(&sl.src[i], p->dpitch[i] * p->rows[i] + 256);
+			if (err == hipSuccess && p->has_dst) err = hipMalloc(&sl.dst[i], p->ddpitch[i] * p->rows[i] + 256);
+			if (!p->has_dst) sl.dst[i] = sl.src[i];
+		}
+		for (hipEvent_t* ev : {&sl.up_done, &sl.run_done, &sl.down_done})
+			if (err == hipSuccess) err = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+	}
+	if (err != hipSuccess)
+	{
+		pipe_free(p.release());
+		return fail((int)err, "%s: the ring of %u slots -> %s", who, d.slots ? d.slots : 3, hipGetErrorString(err));
+	}
+	g_pipes_release = pipes_release;
+	g_pipes.push_back(p.get());
+	*out = p.release();
+	return 0;
+}
+
+int vfgs_hip_host_pipe_submit(vfgs_hip_host_pipe* p, const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst, const vfgs_hip_model* model,
+                              const uint32_t* seed, uint64_t* ticket)
+{
+	std::unique_lock<std::mutex> g(g_mu);
+	const char* const who = "vfgs_hip_host_pipe_submit";
+	if (!p || !src || !ticket) return fail(43, "%s: null %s", who, !p ? "pipe" : !src ? "source" : "ticket pointer");
+	if (!pipe_live(p)) return fail(43, "%s: not an open pipe (closed, or gone with vfgs_hip_shutdown?)", who);
+	// the slot this picture takes: nobody may still sleep on its events (they wake when the slot's previous picture is home, which is what
+	// this call would wait for anyway); the lock is free meanwhile, so everything else is looked at behind it
+	while (p->slot[p->issued % p->nslots].sleepers)
+	{
+		g_pipe_cv.wait(g);
+		if (!pipe_live(p)) return fail(43, "%s: the pipe was closed during the call", who);
+	}
+	State& s = g_states[0];
+	if (g_ndev > 1) return fail(43, "%s: %d devices are set (vfgs_hip_init_devices); a pipe runs on one", who, g_ndev);
+	if (s.ov.active) return fail(43, "%s: an overlap region is open; the pipe's launches run on its own stream", who);
+	if (s.bs != p->bs || s.csubx != p->csubx || s.csuby != p->csuby)
+		return fail(43, "%s: the pipe was opened at depth %d, chroma subsampling %d,%d; programmed: depth %d, %d,%d", who, 8 + p->bs, p->csubx, p->csuby,
+		            8 + s.bs, s.csubx, s.csuby);
+	if (p->has_dst != (dst != nullptr))
+		return fail(43, p->has_dst ? "%s: no destination, and the pipe was opened with destination strides" : "%s: a destination, and the pipe was opened in place", who);
+	if (!src->Y || !src->U || !src->V || (dst && (!dst->Y || !dst->U || !dst->V))) return pipe_passes(who, fail(18, "frame list: frame 0 has a null plane"));
+	if (dst)
+	{
+		// a destination plane that shares bytes with another one, or with a plane of the source (which stays untouched)
+		const void* pl[6] = {dst->Y, dst->U, dst->V, src->Y, src->U, src->V};
+		for (int a = 0; a < 3; a++)
+			for (int b = a + 1; b < 6; b++)
+			{
+				const uintptr_t lo = (uintptr_t)pl[a], hi = lo + (p->rows[a] - 1) * p->hpitch[a] + p->drowlen[a];
+				const int c = b % 3;
+				const uintptr_t lo2 = (uintptr_t)pl[b], hi2 = lo2 + (p->rows[c] - 1) * (b < 3 ? p->hpitch[c] : p->spitch[c]) + (b < 3 ? p->drowlen[c] : p->rowlen[c]);
+				if (lo < hi2 && lo2 < hi)
+					return pipe_passes(who, fail(18, b < 3 ? "frame list: destination planes of frames 0 and 0 overlap" : "frame list: a source plane of frame 0 shares bytes with a destination plane of frame 0"));
+			}
+	}
+	if (int e = ensure_init(-1)) return e;
+	S().gen++;
+	S().la.valid = false;
+	vfgs_hip_host_pipe::Slot& sl = p->slot[p->issued % p->nslots];
+	const vfgs_hip_frame_ptrs ds = {sl.src[0], sl.src[1], sl.src[2]}, dd = {sl.dst[0], sl.dst[1], sl.dst[2]};
+	const vfgs_hip_frame_ptrs* const dsp = &ds;
+	const vfgs_hip_frame_ptrs* const ddp = p->has_dst ? &dd : &ds;
+	// everything that refuses the matching device call, before anything is queued or moves
+	if (int e = pipe_device_call(p, dsp, ddp, model, seed, true)) return pipe_passes(who, e);
+
+	State::HostPipe& P = s.pipe;
+	int rc = 0;
+	auto hip = [&](hipError_t e, const char* what) {
+		if (e != hipSuccess && !rc) rc = fail((int)e, "%s: %s -> %s", who, what, hipGetErrorString(e));
+		return e == hipSuccess;
+	};
+	// back-pressure: the slot's previous picture comes home first (no error; with pinned memory the only place a submit waits)
+	if (sl.ticket > p->home)
+	{
+		if (hip(hipEventSynchronize(sl.down_done), "hipEventSynchronize")) p->home = sl.ticket;
+		else { pipe_drain(s, p); return rc; }
+	}
+	const void* const from[3] = {src->Y, src->U, src->V};
+	void* const to[3] = {dst ? dst->Y : src->Y, dst ? dst->U : src->U, dst ? dst->V : src->V};
+	const void* const back[3] = {sl.dst[0], sl.dst[1], sl.dst[2]};
+	bool ok = hip(copy_planes(sl.src, p->dpitch, from, p->spitch, p->rowlen, p->rows, hipMemcpyHostToDevice, P.up), "hipMemcpy2DAsync (upload)") &&
+	          hip(hipEventRecord(sl.up_done, P.up), "hipEventRecord") && hip(hipStreamWaitEvent(P.run, sl.up_done, 0), "hipStreamWaitEvent");
+	if (ok)
+	{
+		InternalLaunch mark;
+		if (int e = pipe_device_call(p, dsp, ddp, model, seed, false)) { rc = pipe_passes(who, e); ok = false; }
+	}
+	ok = ok && hip(hipEventRecord(sl.run_done, P.run), "hipEventRecord") && hip(hipStreamWaitEvent(P.down, sl.run_done, 0), "hipStreamWaitEvent") &&
+	     hip(copy_planes(to, p->hpitch, back, p->ddpitch, p->drowlen, p->rows, hipMemcpyDeviceToHost, P.down), "hipMemcpy2DAsync (download)") &&
+	     hip(hipEventRecord(sl.down_done, P.down), "hipEventRecord");
+	if (!ok)
+	{
+		// part of the picture may be queued, and copies into the caller's memory may be in flight: everything comes to rest before the error returns
+		pipe_drain(s, p);
+		return rc;
+	}
+	sl.ticket = *ticket = ++p->issued;
+	return 0;
+}
+
+int vfgs_hip_host_pipe_wait(vfgs_hip_host_pipe* p, uint64_t ticket)
+{
+	std::unique_lock<std::mutex> g(g_mu);
+	const char* const who = "vfgs_hip_host_pipe_wait";
+	if (!pipe_live(p)) return fail(43, "%s: %s", who, p ? "not an open pipe (closed, or gone with vfgs_hip_shutdown?)" : "null pipe");
+	if (ticket == 0 || ticket > p->issued) return fail(43, "%s: ticket %llu was never issued (%llu so far)", who, (unsigned long long)ticket, (unsigned long long)p->issued);
+	if (ticket <= p->home) return 0;
+	if (int e = ensure_init(-1)) return e;
+	// (a ticket that is not home yet still has its slot: a submit takes a slot only after its picture came home)
+	vfgs_hip_host_pipe::Slot& sl = p->slot[(ticket - 1) % p->nslots];
+	const hipEvent_t ev = sl.down_done;
+	sl.sleepers++; p->sleepers++; g_pipe_sleepers++;
+	g.unlock();      // asleep without the library's lock: another thread submits meanwhile
+	const hipError_t e = hipEventSynchronize(ev);
+	g.lock();
+	sl.sleepers--; p->sleepers--; g_pipe_sleepers--;
+	g_pipe_cv.notify_all();
+	if (e != hipSuccess) return fail((int)e, "%s: hipEventSynchronize -> %s", who, hipGetErrorString(e));
+	p->home = std::max(p->home, ticket);      // (the downloads complete in the order of the submits: every earlier picture is home too)
+	return 0;
+}
+
+int vfgs_hip_host_pipe_close(vfgs_hip_host_pipe* p)
+{
+	std::unique_lock<std::mutex> g(g_mu);
+	const char* const who = "vfgs_hip_host_pipe_close";
+	auto it = std::find(g_pipes.begin(), g_pipes.end(), p);
+	if (!p || it == g_pipes.end()) return fail(43, "%s: %s", who, p ? "not an open pipe (closed before, or gone with vfgs_hip_shutdown?)" : "null pipe");
+	g_pipes.erase(it);                        // from here on the handle is refused; the threads asleep on its events finish first
+	g_pipe_cv.wait(g, [p] { return p->sleepers == 0; });
+	if (g_states[0].inited && ensure_init(-1) == 0) pipe_drain(g_states[0], p);
+	pipe_free(p);
+	return 0;
 }
 
 void* vfgs_hip_host_alloc(uint64_t bytes)

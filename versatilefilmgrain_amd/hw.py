@@ -152,6 +152,10 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_line_lookahead.restype = None
     lib.vfgs_hip_declare_frame.argtypes = [vp, vp, vp, u, u, u, u]
     lib.vfgs_hip_add_grain_frames_host.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u, u, u, u, u]
+    lib.vfgs_hip_host_pipe_open.argtypes = [C.POINTER(HostPipeDesc), C.POINTER(vp)]
+    lib.vfgs_hip_host_pipe_submit.argtypes = [vp, fp, fp, vp, sp, C.POINTER(C.c_uint64)]
+    lib.vfgs_hip_host_pipe_wait.argtypes = [vp, C.c_uint64]
+    lib.vfgs_hip_host_pipe_close.argtypes = [vp]
     lib.vfgs_hip_host_alloc.argtypes = [C.c_uint64]
     lib.vfgs_hip_host_alloc.restype = vp
     lib.vfgs_hip_host_free.argtypes = [vp]
@@ -182,6 +186,12 @@ class FramePtrs(C.Structure):
     _fields_ = [("Y", C.c_void_p), ("U", C.c_void_p), ("V", C.c_void_p)]
 
 
+class HostPipeDesc(C.Structure):
+    """include/vfgs_hip.h: vfgs_hip_host_pipe_desc."""
+    _fields_ = [("width", C.c_uint), ("height", C.c_uint), ("stride", C.c_uint), ("cstride", C.c_uint), ("dst_stride", C.c_uint),
+                ("dst_cstride", C.c_uint), ("dst8", C.c_int), ("slots", C.c_uint)]
+
+
 class SpFrame(C.Structure):
     """include/vfgs_hip.h: vfgs_hip_sp_frame (device pointers to line 0 of a semi-planar frame's luma plane and its plane of Cb/Cr pairs)."""
     _fields_ = [("Y", C.c_void_p), ("UV", C.c_void_p)]
@@ -209,6 +219,7 @@ EXPORTS = [
     "vfgs_hip_model_capture", "vfgs_hip_model_capture_mix", "vfgs_hip_model_chroma_mix", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
     "vfgs_hip_add_grain_sp_frame_list_models_dev", "vfgs_hip_model_image", "vfgs_hip_get_model_build_stats",
     "vfgs_hip_add_grain_frame_list_models_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_models_copy8_dev",
+    "vfgs_hip_host_pipe_open", "vfgs_hip_host_pipe_submit", "vfgs_hip_host_pipe_wait", "vfgs_hip_host_pipe_close",
 ]
 
 
@@ -578,6 +589,13 @@ class VfgsHip:
         arr = lambda ps: (C.c_void_p * n)(*ps)
         self._ck(self.lib.vfgs_hip_add_grain_frames_host(arr(Ys), arr(Us), arr(Vs), n, width, height, stride, cstride))
 
+    def host_pipe(self, width, height, stride, cstride, dst_stride=0, dst_cstride=0, dst8=False, slots=0):
+        """A pipe for pictures in host memory that arrive one at a time, each with its own model and seed (include/vfgs_hip.h:
+        vfgs_hip_host_pipe_open): an object with submit(src, dst=None, model=None, seed=None) -> ticket, wait(ticket) and close(), also a
+        context manager.  dst_stride = dst_cstride = 0: in place; dst8: planar 8-bit destination of a 10- or 12-bit pipe; slots: pictures
+        in flight (0 = 3, else 2..8)."""
+        return HostPipe(self, HostPipeDesc(width, height, stride, cstride, dst_stride, dst_cstride, 1 if dst8 else 0, slots))
+
     def host_alloc(self, nbytes):
         p = self.lib.vfgs_hip_host_alloc(nbytes)
         if not p:
@@ -624,3 +642,39 @@ class VfgsHip:
         name = C.create_string_buffer(128)
         self._ck(self.lib.vfgs_hip_device_info(C.byref(cu), C.byref(lds), C.byref(clk), name, 128))
         return {"cu_count": cu.value, "lds_per_cu": lds.value, "clock_khz": clk.value, "name": name.value.decode()}
+
+
+class HostPipe:
+    """An open vfgs_hip_host_pipe (VfgsHip.host_pipe).  src / dst: (Y, U, V) HOST addresses of line 0 of the planes; they stay valid and
+    untouched until wait(ticket) has returned.  model: a handle of model_capture / models_from_* (None: the programmed state as it is
+    now), which may be released as soon as submit returns; seed: what vfgs_set_seed would get (None: the running seed sequence)."""
+
+    def __init__(self, hip, desc):
+        self._hip, self.desc = hip, desc
+        h = C.c_void_p()
+        hip._ck(hip.lib.vfgs_hip_host_pipe_open(C.byref(desc), C.byref(h)))
+        self.handle = h.value
+
+    def submit(self, src, dst=None, model=None, seed=None):
+        s = FramePtrs(*src)
+        d = None if dst is None else C.byref(FramePtrs(*dst))
+        sd = None if seed is None else C.byref(C.c_uint32(int(seed) & 0xFFFFFFFF))
+        t = C.c_uint64(0)
+        self._hip._ck(self._hip.lib.vfgs_hip_host_pipe_submit(self.handle, C.byref(s), d, model, sd, C.byref(t)))
+        return t.value
+
+    def wait(self, ticket):
+        self._hip._ck(self._hip.lib.vfgs_hip_host_pipe_wait(self.handle, ticket))
+
+    def close(self):
+        """Drains the pipe and frees its ring; a second close is a no-op."""
+        if self.handle is not None:
+            h, self.handle = self.handle, None
+            self._hip._ck(self._hip.lib.vfgs_hip_host_pipe_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
