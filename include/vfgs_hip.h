@@ -334,7 +334,7 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
  * message -- the mix needs the luma over a UV row in the UV workgroup's ring (as in grain_sp_mix_kernel) on top of the planar loads, which
  * is not built; a caller with a mix grains planar with the calls that honour it.  An empty list is no call at all.
  * Out of scope, on purpose: the mix, stripe / part forms, host-memory entry points, 4:4:4, widths above 8192, and the reverse direction
- * (a surface in, planes out). */
+ * (a surface in, planes out).  A model per picture: vfgs_hip_add_grain_frame_list_models_to_sp_dev / _to_sp8_dev below. */
 int vfgs_hip_add_grain_frame_list_to_sp_dev(const vfgs_hip_frame_ptrs* src,      /* Y, U, V: planar, low-aligned */
                                             const vfgs_hip_sp_frame* dst,        /* Y, UV */
                                             const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
@@ -433,7 +433,8 @@ void vfgs_hip_get_model_build_stats(uint64_t out[8]);
  * that carries a mix adds no refusal of its own: depth and form were checked where the mix was attached.  An empty list is no call at all.
  * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination under a mix (without one:
  * vfgs_hip_add_grain_frame_list_models_copy8_dev below), stripe / part forms, widths above 8192, persistent luma workgroups (1080p
- * general-form luma runs without them here).  Semi-planar surfaces have the call below; pictures in host memory have
+ * general-form luma runs without them here).  Semi-planar surfaces have the call below, planar pictures onto semi-planar surfaces
+ * vfgs_hip_add_grain_frame_list_models_to_sp_dev / _to_sp8_dev further down; pictures in host memory have
  * vfgs_hip_host_pipe_submit, where semi-planar host surfaces and several devices are still out. */
 int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_frame_ptrs* dst,
                                              const vfgs_hip_model* const* models,     /* nframes entries */
@@ -464,7 +465,8 @@ int vfgs_hip_add_grain_frame_list_models_dev(const vfgs_hip_frame_ptrs* src, con
  * programmed one, an active PROGRAMMED chroma mix ("chroma mix" in the message).  Where several apply: the list checks, then 40, then 41.
  * An empty list is no call at all.
  * Out of scope, on purpose: depth 12 or general-form models under a mix, the narrowed 8-bit destination under a mix (without one:
- * vfgs_hip_add_grain_sp_frame_list_models_copy8_dev below), a planar source, stripe / part forms, semi-planar surfaces in host memory
+ * vfgs_hip_add_grain_sp_frame_list_models_copy8_dev below), stripe / part forms (a planar source has
+ * vfgs_hip_add_grain_frame_list_models_to_sp_dev below), semi-planar surfaces in host memory
  * (vfgs_hip_host_pipe_submit takes planar pictures), several devices, 4:4:4, widths above 8192. */
 int vfgs_hip_add_grain_sp_frame_list_models_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                                 const vfgs_hip_model* const* models,   /* nframes entries, host memory */
@@ -528,8 +530,8 @@ int vfgs_hip_add_grain_frame_list_models_copy8_dev(const vfgs_hip_frame_ptrs* sr
  * destination plane or with ANY source plane of the call, its own frame's included; 7; 5 / 6 / 8; 15; 6 / 8 for dst_stride and
  * dst_uv_stride), then depth 8: 16, then 40 (csubx != 2, a bad sample_shift, width > 8192), then 41 as above (width aside, which is 40
  * here).  An empty list is no call at all.
- * Out of scope, on purpose: models that carry a mix, a planar source (the _to_sp8 call has no form with models), 4:4:4, widths above
- * 8192, stripe / part forms, semi-planar surfaces in host memory (vfgs_hip_host_pipe_submit takes planar pictures), several devices. */
+ * Out of scope, on purpose: models that carry a mix, 4:4:4, widths above 8192, stripe / part forms (a planar source has
+ * vfgs_hip_add_grain_frame_list_models_to_sp8_dev below), semi-planar surfaces in host memory (vfgs_hip_host_pipe_submit takes planar pictures), several devices. */
 int vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_sp_frame* dst,
                                                       const vfgs_hip_model* const* models,   /* nframes entries, host memory */
                                                       const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
@@ -538,6 +540,56 @@ int vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(const vfgs_hip_sp_frame* s
                                                       unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
                                                       unsigned sample_shift,                 /* 0, or 16 - depth */
                                                       void* stream);
+
+/* A MODEL PER PICTURE FROM PLANAR PICTURES ONTO SEMI-PLANAR SURFACES: the software-decoder pipeline -- dav1d hands out yuv420p10le pictures,
+ * each with its own AV1 film grain parameters and grain_seed, and the player wants P010 or NV12 on the device.  src / dst / stride / cstride /
+ * dst_stride / dst_uv_stride / sample_shift exactly as in vfgs_hip_add_grain_frame_list_to_sp_dev (planar, low-aligned pictures in; Y and UV
+ * in the depth's container out, strides in containers; never in place); models and seeds exactly as in
+ * vfgs_hip_add_grain_frame_list_models_dev: the same handles -- vfgs_hip_model_capture, vfgs_hip_models_from_afgs1, vfgs_hip_models_from_sei
+ * alike -- general-form and one-pattern models both, seeds == NULL: one seed sequence.  The containers written, the bytes left alone and the
+ * four seed registers afterwards are those of
+ *     for f in list order:
+ *         program the state models[f] was made from;
+ *         if (seeds) vfgs_set_seed(seeds[f]);
+ *         vfgs_hip_add_grain_frame_list_to_sp_dev(&src[f], &dst[f], NULL, 1, ...)
+ * and the library's own programmed state is UNCHANGED by the call.  Formats: 4:2:0 and 4:2:2 at depths 8, 10 and 12.
+ * Launches: one per run of at most 32 consecutive frames whose models share (one_y, one_c); a change of form starts a new launch, a change
+ * of patterns, LUTs, scale shift or range does not.  No kernel of their own: the launches are those of the programmed call, whose kernels
+ * take image, clip bounds and shift from each frame's model where a launch names models; both components of a Cb/Cr pair take the frame's
+ * chroma bounds.  vfgs_hip_last_launch_info(): listed = 1, in_place = 0, out8 = 0, kernel grain_p2sp_kernel<depth,csuby,oney,onec>;
+ * `launches` counts every run.  No copy is queued in front of a launch on account of models.  Inside an overlap region the call alternates
+ * over the two internal streams like every device-pointer call; it runs on the primary device.
+ * Refused before anything changes (a refused call does not reseed).  Where several apply, in this order -- that of
+ * vfgs_hip_add_grain_frame_list_to_sp_dev, then the models' checks: error 40 (csubx != 2, a bad sample_shift, width > 8192); 18 a null
+ * list; 6 / 8 a destination stride too small / a destination pitch that is no multiple of 16 bytes; the list checks (18 a null plane; 7;
+ * 5 / 6 / 8 / 17 source geometry -- except that the scale shift that counts is each model's, checked where the model was made; 18 a
+ * destination plane that shares bytes with another destination plane or with ANY source plane of the call); 15; then error 41 with a
+ * message that names the cause: models == NULL, a NULL or released entry, a model of another depth or chroma format than the programmed
+ * one, an active PROGRAMMED chroma mix, a model in the list that CARRIES a mix ("chroma mix" in both messages: the to-surface kernels have
+ * no form with the luma over their chroma rows).  An empty list is no call at all.
+ * Out of scope, on purpose: models that carry a mix or a programmed mix, 4:4:4 surfaces, widths above 8192, stripe / part forms, a
+ * semi-planar destination for vfgs_hip_host_pipe_submit, several devices. */
+int vfgs_hip_add_grain_frame_list_models_to_sp_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst,
+                                                   const vfgs_hip_model* const* models,   /* nframes entries, host memory */
+                                                   const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
+                                                   unsigned nframes, unsigned width, unsigned height,
+                                                   unsigned stride, unsigned cstride,            /* source, in samples */
+                                                   unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in containers */
+                                                   unsigned sample_shift,                 /* 0, or 16 - depth (P010: 6, P012: 4); 0 only at depth 8 */
+                                                   void* stream);
+
+/* ... with the NARROWED 8-BIT DESTINATION: planar 10- or 12-bit pictures in, NV12 / NV16 out, a model with every picture.  As above around
+ * the one-frame vfgs_hip_add_grain_frame_list_to_sp8_dev: dst[f] a semi-planar picture of bytes, dst_stride / dst_uv_stride in BYTES; the
+ * bytes are (uint8)((v + 2) >> 2) of the grained, clipped sample v at depth 10, (uint8)((v + 8) >> 4) at depth 12.
+ * vfgs_hip_last_launch_info(): out8 = 1, kernel grain_p2sp8_kernel<depth,csuby,oney,onec>.  Refusals as above, in the same order; depth 8:
+ * error 16, behind 40 and in front of everything else, as in vfgs_hip_add_grain_frame_list_to_sp8_dev. */
+int vfgs_hip_add_grain_frame_list_models_to_sp8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst,
+                                                    const vfgs_hip_model* const* models,   /* nframes entries, host memory */
+                                                    const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
+                                                    unsigned nframes, unsigned width, unsigned height,
+                                                    unsigned stride, unsigned cstride,            /* source, in 16-bit samples */
+                                                    unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
+                                                    void* stream);
 
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).

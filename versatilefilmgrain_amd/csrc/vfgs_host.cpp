@@ -1662,9 +1662,10 @@ int Launch::admit()
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (p2sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
-	if (mr && (!list || p2sp || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
+	if (mr && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || width > (unsigned)vfgs::kTileBlocks * 16 || mix_active() || &s != &g_states[0]))
 		return fail(19, "internal: a model per frame goes with listed whole frames, planar or semi-planar, of at most %d samples a row, without a programmed chroma mix", vfgs::kTileBlocks * 16);
 	// (the narrowed destination with a model per frame: the OUT8 kernels of rw / sp8 decide at run time; the kernels of the mix have no such form -- refused with 41 at the entry)
+	// (a planar source onto a surface with a model per frame: the kernels of p2sp / p2sp8 decide at run time; models that carry a mix are refused below, 41 at the entry)
 	if (mr && dg.out8 && mr->mix) return fail(19, "internal: models that carry a mix were admitted for a narrowed destination");
 	if (part_h == 0 && seeds && nframes) load_seed(s, seeds[nframes - 1]);     // (the single-frame call of a part without lines returns here too: the seed alone)
 	if (part_h == 0 || nframes == 0) { nothing = true; return 0; }
@@ -1705,7 +1706,7 @@ int Launch::admit()
 	// (a model per frame: the run's models carry a mix of their own -- depth and form were checked where it was attached -- and the programmed
 	// one, refused above, is not looked at)
 	mix = mr ? mr->mix : mix_active();
-	if (mix && p2sp) return fail(19, "internal: a planar source with a semi-planar destination under a chroma mix");     // (refused with code 40 at the entry)
+	if (mix && p2sp) return fail(19, "internal: a planar source with a semi-planar destination under a chroma mix");     // (refused with code 40 at the entry; models that carry one: 41)
 	const int mix_code = sp ? 40 : 38;
 	const char* const mix_who = sp ? "semi-planar frames: " : "";
 	if (mix && s.bs == 4)
@@ -1928,7 +1929,7 @@ int Launch::plan_grid()
 int Launch::launch()
 {
 	// the kernel of this call (vfgs_layout.h KernelKey), formed once: admit() has refused a model per frame under a programmed mix, models that carry a
-	// mix with a narrowed destination, a model per frame from a planar source onto a surface, and a planar source under a mix
+	// mix with a narrowed destination, and a planar source under a mix (programmed, or carried by a model)
 	using vfgs::Family;
 	key = vfgs::KernelKey{8 + s.bs, s.csubx, s.csuby, dg.out8, img_one_y, img_one_c, wide, persist,
 	                      p2sp ? (dg.out8 ? Family::p2sp8 : Family::p2sp)
@@ -1938,9 +1939,11 @@ int Launch::launch()
 	const bool mix_models = mr && mix;
 	// (a model per frame with the narrowed destination: the OUT8 kernels of ordinary rows without persistence, which decide the same way)
 	const bool out8_models = mr && !mix && (key.family == Family::rw || key.family == Family::sp8) && key.out8 && !key.wide && !key.persist;
-	if (mr && !mix_models && !out8_models && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
+	// (a model per frame from a planar source onto a surface: the kernels of p2sp / p2sp8, every one of which decides the same way)
+	const bool p2sp_models = mr && !mix && (key.family == Family::p2sp || key.family == Family::p2sp8);
+	if (mr && !mix_models && !out8_models && !p2sp_models && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
 	if (mix_models && (key.out8 || key.wide)) return fail(19, "internal: models that carry a mix were admitted for a narrowed destination or rows walked in parts");
-	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models || out8_models);
+	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models || out8_models || p2sp_models);
 	a.models_kernel = ff.models_kernel; a.mix_kernel = ff.mix_kernel; a.sp_kernel = ff.sp_kernel;
 	if (sp || p2sp) a.sp_shift2 = sample_shift * 0x10001u;
 	if (mix)
@@ -3908,11 +3911,13 @@ static int check_out8_rows(const State& s, unsigned width, unsigned dst_stride, 
 }
 
 // ... and behind check_models: the kernels of the mix have no narrowed form with models (nframes live models, check_models has seen to that)
-static int check_models_without_mix(const char* who, const vfgs_hip_model* const* models, unsigned nframes)
+// (why: what the call lacks for such a model -- the calls from a planar source onto a surface say their own)
+static int check_models_without_mix(const char* who, const vfgs_hip_model* const* models, unsigned nframes,
+                                    const char* why = "the kernels of the mix have no narrowed form with a model per frame")
 {
 	for (unsigned f = 0; f < nframes; f++)
 		if (models[f]->has_mix)
-			return fail(41, "%s: the model of frame %u carries a chroma mix; the kernels of the mix have no narrowed form with a model per frame", who, f);
+			return fail(41, "%s: the model of frame %u carries a chroma mix; %s", who, f, why);
 	return 0;
 }
 
@@ -3961,15 +3966,19 @@ int vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(const vfgs_hip_sp_frame* s
 // A planar source, a semi-planar destination (vfgs_hip.h): what a software decoder hands out goes onto the surface a display takes.  The planar
 // list call with a destination geometry of its own whose U and V planes are the UV plane; what the semi-planar calls refuse for their
 // destination is refused here with their codes, before anything moves.
-static int run_to_sp(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes, const GrainCall& c, void* stream)
+// with_models (vfgs_hip_add_grain_frame_list_models_to_sp_dev / _to_sp8_dev): a model per frame -- the same checks in the same order, then those of
+// the calls with models (41: a programmed mix is theirs to refuse, and so is a model that carries one); launch_list cuts the list into runs of one form.
+static int run_to_sp(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const uint32_t* seeds, unsigned nframes, const GrainCall& c, void* stream,
+                     const bool with_models = false, const vfgs_hip_model* const* models = nullptr)
 {
 	State& s = S();
 	s.gen++;
 	if (int e = ensure_init(-1)) return e;
 	if (nframes == 0) return 0;
-	if (int e = check_semiplanar("planar to semi-planar", s, c.sample_shift, c.width)) return e;
+	const char* const who = with_models ? "planar to semi-planar with models" : "planar to semi-planar";
+	if (int e = check_semiplanar(who, s, c.sample_shift, c.width)) return e;
 	if (c.dg.out8 && s.bs == 0) return fail(16, "8-bit output needs a 10- or 12-bit path (vfgs_set_depth(10) or (12))");
-	if (mix_active())
+	if (!with_models && mix_active())
 		return fail(40, "planar to semi-planar: a chroma mix is active; these kernels have no form with the luma over their chroma rows (grain planar with the mix calls)");
 	if (!src || !dst) return fail(18, "frame list: null list");
 	// (the destination's pitches, with the codes of the calls it is carried over from: a UV row is as many containers as the luma row)
@@ -3979,7 +3988,14 @@ static int run_to_sp(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* ds
 	if ((c.dg.stride * dsz) % 16 || (c.dg.cstride * dsz) % 16) return fail(8, "destination row pitches must be multiples of 16 bytes");
 	const std::vector<vfgs_hip_frame_ptrs> pd = three_planes(dst, nframes);
 	ListCall l(src, pd.data(), nframes, seeds, stream, c);
+	if (with_models) l.with(models);     // (before the list checks: the scale shift that counts is each model's)
 	if (int e = check_list(l)) return e;
+	if (with_models)
+	{
+		if (int e = check_models_window(l)) return e;
+		if (int e = check_models(who, s, models, nframes, 0)) return e;     // (width: refused above, under 40)
+		if (int e = check_models_without_mix(who, models, nframes, "the to-surface kernels have no form with the luma over their chroma rows")) return e;
+	}
 	return launch_list(l);
 }
 
@@ -3997,6 +4013,26 @@ int vfgs_hip_add_grain_frame_list_to_sp8_dev(const vfgs_hip_frame_ptrs* src, con
 {
 	std::lock_guard<std::mutex> g(g_mu);
 	return run_to_sp(src, dst, seeds, nframes, GrainCall().rows(width, stride, cstride).whole(height).to(Surface::to_semiplanar, 0).dst_rows(true, dst_stride, dst_uv_stride), stream);
+}
+
+// ... with A MODEL PER FRAME (vfgs_hip.h): what a software decoder hands out, each picture with its own film grain parameters, onto surfaces.
+// No kernel of their own: grain_p2sp_kernel / grain_p2sp8_kernel take image, bounds and shift from the frame's model where a launch names models.
+int vfgs_hip_add_grain_frame_list_models_to_sp_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const vfgs_hip_model* const* models,
+                                                   const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                                   unsigned cstride, unsigned dst_stride, unsigned dst_uv_stride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return run_to_sp(src, dst, seeds, nframes, GrainCall().rows(width, stride, cstride).whole(height).to(Surface::to_semiplanar, sample_shift).dst_rows(false, dst_stride, dst_uv_stride), stream,
+	                 true, models);
+}
+
+int vfgs_hip_add_grain_frame_list_models_to_sp8_dev(const vfgs_hip_frame_ptrs* src, const vfgs_hip_sp_frame* dst, const vfgs_hip_model* const* models,
+                                                    const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                                    unsigned cstride, unsigned dst_stride, unsigned dst_uv_stride, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return run_to_sp(src, dst, seeds, nframes, GrainCall().rows(width, stride, cstride).whole(height).to(Surface::to_semiplanar, 0).dst_rows(true, dst_stride, dst_uv_stride), stream,
+	                 true, models);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,

@@ -695,6 +695,8 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     KernelArgs::mix).  A value of its own so that the instantiations every other kernel uses stay what they were.
 //     MODELS = 2 with OUT8 (every plane of grain_rw_kernel<.., OUT8, .., !WIDE, !PERSIST>, the luma planes of grain_sp8_kernel): the same
 //     run-time decision for the narrowed destination -- the programmed _copy8 calls and the _models_copy8 lists share their kernels.
+//     MODELS = 2 with SP = 2 (the luma planes of grain_p2sp_kernel / grain_p2sp8_kernel): the same run-time decision from a planar source onto a
+//     surface -- the programmed _to_sp / _to_sp8 calls and the _models_to_sp / _models_to_sp8 lists share their kernels.
 template <int DEPTH, int BW, int SUBX, int SUBY, int RS, int IMG_BYTES, bool ONE, int NEG, int NARROW, bool OUT8, bool WIDE, bool PERSIST, bool MIX = false, int SP = 0, int MODELS = 0>
 __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTable& ft, const PlaneDesc& pd, uint8_t* lds, const int comp, const int f_in, const int r_in,
                                              const uint32_t img_off, const uint32_t bank_off, const uint32_t lut_off, const int lane, const int wave)
@@ -723,7 +725,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!(PERSIST && (WIDE || NARROW != 0)), "persistent workgroups walk ordinary rows");
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
-	static_assert(!MODELS || (!WIDE && !PERSIST && (!MIX || MODELS == 2) && SP != 2 && (!OUT8 || (MODELS == 2 && !MIX))), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup; under the mix and with the narrowed destination: decided at run time");
+	static_assert(!MODELS || (!WIDE && !PERSIST && (!MIX || MODELS == 2) && (SP != 2 || (MODELS == 2 && !MIX)) && (!OUT8 || (MODELS == 2 && !MIX))), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup; under the mix, with the narrowed destination and from a planar source onto a surface: decided at run time");
 	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
@@ -1395,6 +1397,8 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // then also supplies both components' mix (the two mix words of its record), and KernelArgs::mix is not read.
 // MODELS = 2 with OUT8 (UV workgroups of grain_sp8_kernel): the same run-time decision without a mix; BOTH components of the 16-byte unit of
 // Cb/Cr byte pairs are clipped with the frame's chroma bounds (lo2 / hi2 below are one pair for the two grain_unit calls of a position).
+// MODELS = 2 with PLANAR (UV workgroups of grain_p2sp_kernel / grain_p2sp8_kernel): the same run-time decision; both components of a Cb/Cr pair
+// take the frame's chroma bounds.
 template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, int MODELS = 0>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
@@ -1414,7 +1418,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr int KD = OUT8 ? K / 2 : K;                 // ... and how many of them belong to the lane before its own
 	static_assert(!OUT8 || (DEPTH > 8 && K % 2 == 0 && !MIX), "the narrowed destination exists for 16-bit containers, without the mix");
 	static_assert(!PLANAR || !MIX, "a planar source has no mix form");
-	static_assert(!MODELS || (!PLANAR && (OUT8 ? (MODELS == 2 && !MIX) : MIX == (MODELS == 2))), "a model per frame: the plain UV walk; under the mix and with the narrowed destination: decided at run time");
+	static_assert(!MODELS || ((OUT8 || PLANAR) ? (MODELS == 2 && !MIX) : MIX == (MODELS == 2)), "a model per frame: the plain UV walk; under the mix, with the narrowed destination and from a planar source: decided at run time");
 	constexpr bool DGEO = OUT8 || PLANAR;                // the destination has a geometry of its own
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
@@ -1908,10 +1912,12 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_p2sp_kerne
 	// for every dispatch; `b` is a copy in registers, never in memory.  Guard: tests/test_code_object_p2sp_cpu.py, private_segment_fixed_size == 0)
 	KernelArgs b = a;
 	b.listed = 1;
+	// (a model per frame -- KernelArgs::models_kernel; vfgs_hip_add_grain_frame_list_models_to_sp_dev, DESIGN.md 4.8 -- is decided at run time in both walks:
+	// MODELS = 2, a wave-uniform branch around the scalar loads of the frame's record; the guard above holds for it too)
 	if (r < b.pd[0].wgs)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, 2, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
-		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, true>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, true, 2>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // ... with the narrowed 8-bit destination (KernelArgs::sp_kernel == 2 AND out8: planar 10 / 12 bit in, NV12 / NV16 out;
@@ -1929,11 +1935,11 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_p2sp8_kern
 	const int r = (int)(blockIdx.x >> a.lfronts);
 	if (f >= a.nframes) return;
 	KernelArgs b = a;
-	b.listed = 1;      // (as in grain_p2sp_kernel)
+	b.listed = 1;      // (as in grain_p2sp_kernel; a model per frame, vfgs_hip_add_grain_frame_list_models_to_sp8_dev, likewise: MODELS = 2 in both walks)
 	if (r < b.pd[0].wgs)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, true, false, false, false, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, true, false, false, false, 2, 2>(b, ft, b.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
 	else
-		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true, true>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, true, true, 2>(b, ft, lds, f, r - b.pd[0].wgs, L.c_off[0], lane, wave);
 }
 
 // The kernels of semi-planar frames under the luma / chroma mix (KernelArgs::sp_kernel AND mix_kernel): all-one-pattern images
@@ -1988,7 +1994,9 @@ static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const Ke
 	// (so do the narrowed kernels of ordinary rows without persistence: grain_rw_kernel<.., out8, .., !wide, !persist> and grain_sp8_kernel)
 	const bool out8_models = (f == Family::rw || f == Family::sp8) && a.models_kernel != 0;
 	if (out8_models && !(k.out8 && !k.wide && !k.persist)) return false;
-	const FamilyFields ff = family_fields(f, mix_models || out8_models);
+	// (and every kernel of a planar source with a semi-planar destination: listed frames with a 16-byte-aligned model image each, held to that below)
+	const bool p2sp_models = (f == Family::p2sp || f == Family::p2sp8) && a.models_kernel != 0;
+	const FamilyFields ff = family_fields(f, mix_models || out8_models || p2sp_models);
 	if (a.models_kernel != ff.models_kernel || a.mix_kernel != ff.mix_kernel || a.sp_kernel != ff.sp_kernel) return false;
 	if (k.wide != (a.nblk > kTileBlocks)) return false;
 	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return false;

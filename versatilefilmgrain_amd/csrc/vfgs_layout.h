@@ -317,6 +317,8 @@ struct KernelArgs {
 	// shift AND the mix are the frame's model's, `mix` below is not read.
 	// With a key of family rw or sp8 that has out8 (neither wide nor persist): the narrowed kernels serve listed frames with a model each the same way
 	// (vfgs_hip_add_grain_frame_list_models_copy8_dev, vfgs_hip_add_grain_sp_frame_list_models_copy8_dev).
+	// With sp_kernel == 2: the kernels of p2sp / p2sp8 serve listed planar frames with a model each onto surfaces the same way
+	// (vfgs_hip_add_grain_frame_list_models_to_sp_dev / _to_sp8_dev).
 	int models_kernel;
 	const uint8_t* tables;    // device image (image_layout)
 	uint32_t cur_bit0;        // stream bit of the register of block 0, first block row of the stripe, frame 0
@@ -408,12 +410,13 @@ constexpr bool family_semiplanar(const Family f) { return f != Family::rw && f !
 // key's: it tells sp8 from sp and p2sp8 from p2sp.
 // with_models: a launch of the two families of the mix that names a model per frame (models that carry a mix; the key has neither out8 nor wide) --
 // the same kernels, which decide at run time where the image, the bounds and the mix come from -- or of rw / sp8 with the narrowed destination
-// (the key has out8, neither wide nor persist; the launcher holds it to that): the OUT8 kernels decide the same way.  Every other family has one answer.
+// (the key has out8, neither wide nor persist; the launcher holds it to that): the OUT8 kernels decide the same way -- or of p2sp / p2sp8 (a planar
+// source onto a surface with a model per frame: every kernel of the two families decides the same way).  Every other family has one answer.
 struct FamilyFields { int models_kernel, mix_kernel, sp_kernel; };
 constexpr FamilyFields family_fields(const Family f, const bool with_models = false)
 {
 	const bool mixf = f == Family::mix || f == Family::sp_mix;
-	const bool run_time = mixf || f == Family::rw || f == Family::sp8;     // the families whose kernels serve programmed launches and models alike
+	const bool run_time = mixf || f == Family::rw || f == Family::sp8 || f == Family::p2sp || f == Family::p2sp8;     // the families whose kernels serve programmed launches and models alike
 	return FamilyFields{f == Family::ml || f == Family::spml || (run_time && with_models), mixf,
 	                    !family_semiplanar(f) ? 0 : ((f == Family::p2sp || f == Family::p2sp8) ? 2 : 1)};
 }

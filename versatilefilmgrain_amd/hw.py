@@ -137,6 +137,8 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_add_grain_sp_frame_list_models_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_models_copy8_dev.argtypes = [fp, fp, C.POINTER(vp), sp, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_sp_frame_list_models_copy8_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_models_to_sp_dev.argtypes = [fp, spf, C.POINTER(vp), sp, u, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_frame_list_models_to_sp8_dev.argtypes = [fp, spf, C.POINTER(vp), sp, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -219,6 +221,7 @@ EXPORTS = [
     "vfgs_hip_model_capture", "vfgs_hip_model_capture_mix", "vfgs_hip_model_chroma_mix", "vfgs_hip_model_release", "vfgs_hip_model_info", "vfgs_hip_add_grain_frame_list_models_dev",
     "vfgs_hip_add_grain_sp_frame_list_models_dev", "vfgs_hip_model_image", "vfgs_hip_get_model_build_stats",
     "vfgs_hip_add_grain_frame_list_models_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_models_copy8_dev",
+    "vfgs_hip_add_grain_frame_list_models_to_sp_dev", "vfgs_hip_add_grain_frame_list_models_to_sp8_dev",
     "vfgs_hip_host_pipe_open", "vfgs_hip_host_pipe_submit", "vfgs_hip_host_pipe_wait", "vfgs_hip_host_pipe_close",
 ]
 
@@ -535,6 +538,31 @@ class VfgsHip:
         arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
         self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_models_copy8_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
                                                                             dst_stride, dst_uv_stride, sample_shift, stream))
+
+    def add_grain_frame_list_models_to_sp_dev(self, src, dst, models, seeds, width, height, stride, cstride, dst_stride, dst_uv_stride,
+                                              sample_shift, stream=0):
+        """Planar frames in, semi-planar surfaces out, a model per picture (what a software decoder hands out, each picture with its own film
+        grain parameters, onto P010 / NV12 ...): src / dst / strides / sample_shift as in add_grain_frame_list_to_sp_dev (never in place),
+        models and seeds as in add_grain_frame_list_models_dev.  Frame f gets the containers of a one-frame add_grain_frame_list_to_sp_dev
+        with models[f]'s state programmed (and, with seeds, vfgs_set_seed(seeds[f]) called); one launch per run of at most 32 frames whose
+        models share the form of their images; the programmed state is unchanged.  VfgsHipError 40: csubx != 2, a bad sample_shift, width
+        > 8192; 41: a null / released model, a model of another depth or chroma format, an active chroma mix, a model that carries a mix;
+        18: a destination that shares bytes with any source plane (include/vfgs_hip.h)."""
+        s, d = self.frame_list(src), self.sp_frame_list(dst)
+        assert len(s) == len(d) == len(models) and (seeds is None or len(seeds) == len(s))
+        arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_models_to_sp_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, cstride,
+                                                                         dst_stride, dst_uv_stride, sample_shift, stream))
+
+    def add_grain_frame_list_models_to_sp8_dev(self, src, dst, models, seeds, width, height, stride, cstride, dst_stride, dst_uv_stride, stream=0):
+        """... with the narrowed 8-bit destination (planar 10 / 12 bit -> NV12 / NV16 with a model per picture): dst frames of bytes, strides in
+        bytes, as in add_grain_frame_list_to_sp8_dev; models and seeds as above.  VfgsHipError 16: depth 8; otherwise as above
+        (include/vfgs_hip.h)."""
+        s, d = self.frame_list(src), self.sp_frame_list(dst)
+        assert len(s) == len(d) == len(models) and (seeds is None or len(seeds) == len(s))
+        arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
+        self._ck(self.lib.vfgs_hip_add_grain_frame_list_models_to_sp8_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, cstride,
+                                                                          dst_stride, dst_uv_stride, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
