@@ -126,7 +126,11 @@ int vfgs_hip_get_chroma_mix(int c, int out[4]);
 /* Device-resident stripe / frame: dY/dU/dV are DEVICE pointers to the first line of the
  * stripe (dU/dV: chroma row y/csuby); 16-byte aligned, pitch*bytes_per_sample % 16 == 0,
  * stride >= 16*ceil(width/16) (the reference writes whole 16-sample blocks, SURVEY 8a
- * quirk 7).  Asynchronous on `stream` (a hipStream_t, may be NULL).  Returns 0 on success. */
+ * quirk 7).  Bytes outside the whole blocks of a row and rows outside the addressed lines -- above a stripe or
+ * part, behind its last line, behind chroma row ceil(height / csuby) - 1 -- are never written or relied upon, in
+ * place or out of place, in this and in every planar call below; the smallest pitch is the whole blocks of the row
+ * in bytes, rounded up to a multiple of 16 (8-bit 4:2:0 of 21 blocks: luma 336, chroma 168 -> 176), and planes may
+ * lie back to back in one allocation.  Asynchronous on `stream` (a hipStream_t, may be NULL).  Returns 0 on success. */
 int vfgs_hip_add_grain_stripe_dev(void* dY, void* dU, void* dV, unsigned y, unsigned width,
                                   unsigned height, unsigned stride, unsigned cstride, void* stream);
 int vfgs_hip_add_grain_frame_dev(void* dY, void* dU, void* dV, unsigned width, unsigned height,
