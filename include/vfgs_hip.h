@@ -337,8 +337,9 @@ int vfgs_hip_add_grain_sp_frame_list_copy8_dev(const vfgs_hip_sp_frame* src, con
  * with another destination plane or with ANY source plane of the call is error 18.  An active chroma mix: error 40, "chroma mix" in the
  * message -- the mix needs the luma over a UV row in the UV workgroup's ring (as in grain_sp_mix_kernel) on top of the planar loads, which
  * is not built; a caller with a mix grains planar with the calls that honour it.  An empty list is no call at all.
- * Out of scope, on purpose: the mix, stripe / part forms, host-memory entry points, 4:4:4, widths above 8192, and the reverse direction
- * (a surface in, planes out).  A model per picture: vfgs_hip_add_grain_frame_list_models_to_sp_dev / _to_sp8_dev below. */
+ * Out of scope, on purpose: the mix, stripe / part forms, host-memory entry points, 4:4:4, widths above 8192.  The reverse direction (a
+ * surface in, planes out): vfgs_hip_add_grain_sp_frame_list_to_planar_dev below.  A model per picture:
+ * vfgs_hip_add_grain_frame_list_models_to_sp_dev / _to_sp8_dev below. */
 int vfgs_hip_add_grain_frame_list_to_sp_dev(const vfgs_hip_frame_ptrs* src,      /* Y, U, V: planar, low-aligned */
                                             const vfgs_hip_sp_frame* dst,        /* Y, UV */
                                             const uint32_t* seeds,      /* NULL: frame f + 1 continues frame f's registers */
@@ -594,6 +595,58 @@ int vfgs_hip_add_grain_frame_list_models_to_sp8_dev(const vfgs_hip_frame_ptrs* s
                                                     unsigned stride, unsigned cstride,            /* source, in 16-bit samples */
                                                     unsigned dst_stride, unsigned dst_uv_stride,  /* destination, in bytes */
                                                     void* stream);
+
+/* SEMI-PLANAR surfaces in, PLANAR pictures out: what a hardware decoder or a capture path hands out (NV12 / NV16 / P010 / P210 / P012) goes
+ * to a consumer that takes planes -- a software encoder (x265, SVT-AV1, VTM read yuv420p / yuv420p10le), the planar calls of this library,
+ * a tensor per plane -- in ONE pass instead of the semi-planar call out of place into a scratch surface, a de-interleave pass and a
+ * shift-down pass (profiles/sp_to_planar.json).
+ *   src[f]       a semi-planar picture: Y and UV, stride / uv_stride in containers, sample_shift -- of the SOURCE -- 0, or 16 - depth
+ *                (P010: 6, P012: 4; only 0 at depth 8), exactly as in vfgs_hip_add_grain_sp_frame_list_dev;
+ *   dst[f]       a planar picture at the programmed depth: Y, U, V with LOW-aligned samples, as the planar list calls take them;
+ *                dst_stride, dst_cstride in samples, dst_stride >= 16 * ceil(width / 16), dst_cstride >= 8 * ceil(width / 16), pitches in
+ *                bytes multiples of 16, pointers 16-byte aligned; planes may lie back to back at the smallest legal pitches;
+ *   seeds        NULL: one seed sequence; else a seed per picture.
+ * Samples: every written sample is what vfgs_hip_add_grain_sp_frame_list_dev writes out of place for the same container of src[f], shifted
+ * right by sample_shift; U[i] is from UV[2 i], V[i] from UV[2 i + 1].  Source bits below the shift, and containers above the depth's range,
+ * therefore behave as in that call.  The four seed registers afterwards are that call's.  Only the whole 16-sample blocks of the addressed
+ * rows are written (a chroma row: 8 samples per block and component); everything else in the destination keeps its bytes.  One launch per
+ * 32 frames (vfgs_hip_last_launch_info(): listed = 1, in_place = 0, out8 = 0, kernel grain_sp_kernel<depth,csuby,oney,onec> -- no kernel of
+ * its own: the kernels of the semi-planar call decide at run time where their results go); inside an overlap region the call alternates
+ * over the two internal streams like every other device-pointer call; it runs on the primary device.  General-form and one-pattern models
+ * alike.
+ * Never in place: a destination plane that shares bytes with another destination plane, or with any source plane of the call, is error 18.
+ * Refused before anything changes (a refused call does not reseed), in the order of vfgs_hip_add_grain_frame_list_to_sp_dev with source
+ * and destination swapped: error 40 with a message that names the cause (csubx != 2, a bad sample_shift, width > 8192; an active chroma
+ * mix, "chroma mix" in the message); 18 a null list; 6 / 8 a destination stride too small / a destination pitch that is no multiple of 16
+ * bytes; the list checks (18 a null plane, 7 a misaligned pointer, 5 / 6 / 8 source geometry, 18 planes that share bytes); 15.  An empty
+ * list is no call at all.
+ * Out of scope, on purpose: the narrowed 8-bit planar destination, the mix (it stays with the calls that honour it: grain the surface with
+ * vfgs_hip_add_grain_sp_frame_list_dev), stripe / part forms, host memory and the host pipe, 4:4:4, widths above 8192, several devices. */
+int vfgs_hip_add_grain_sp_frame_list_to_planar_dev(const vfgs_hip_sp_frame* src,      /* Y, UV: as in vfgs_hip_add_grain_sp_frame_list_dev */
+                                                   const vfgs_hip_frame_ptrs* dst,    /* Y, U, V: planar, LOW-aligned, as the planar list calls take them */
+                                                   const uint32_t* seeds,             /* NULL: one seed sequence; else a seed per picture */
+                                                   unsigned nframes, unsigned width, unsigned height,
+                                                   unsigned stride, unsigned uv_stride,        /* source, in containers */
+                                                   unsigned dst_stride, unsigned dst_cstride,  /* destination, in samples */
+                                                   unsigned sample_shift,             /* of the SOURCE: 0, or 16 - depth; only 0 at depth 8 */
+                                                   void* stream);
+
+/* ... with A MODEL PER PICTURE: models and seeds exactly as in vfgs_hip_add_grain_sp_frame_list_models_dev, everything else as above.  Every
+ * written sample is what that call writes out of place for the same container, shifted right by sample_shift; the seed registers are that
+ * call's; the library's own programmed state is UNCHANGED.  Launches: one per run of at most 32 consecutive frames whose models share
+ * (one_y, one_c); vfgs_hip_last_launch_info(): kernel grain_spml_kernel<depth,csuby,oney,onec>, `launches` counts every run.
+ * Refusals as above, in the same order, except that the scale shift that counts is each model's and that a programmed mix is the models'
+ * to refuse; then, behind 15, error 41 with a message that names the cause: models == NULL, a NULL or released entry, a model of another
+ * depth or chroma format than the programmed one, an active PROGRAMMED chroma mix, a model in the list that CARRIES a mix ("chroma mix" in
+ * both messages; out of scope here: the mix stays with the calls that honour it). */
+int vfgs_hip_add_grain_sp_frame_list_models_to_planar_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_frame_ptrs* dst,
+                                                          const vfgs_hip_model* const* models,   /* nframes entries, host memory */
+                                                          const uint32_t* seeds,                 /* NULL: one seed sequence; else a seed per picture */
+                                                          unsigned nframes, unsigned width, unsigned height,
+                                                          unsigned stride, unsigned uv_stride,        /* source, in containers */
+                                                          unsigned dst_stride, unsigned dst_cstride,  /* destination, in samples */
+                                                          unsigned sample_shift,                 /* of the SOURCE: 0, or 16 - depth; only 0 at depth 8 */
+                                                          void* stream);
 
 /* What a seeded launch uploads, host only (no GPU needed), the counterpart of vfgs_hip_lfsr_segments below: out[f * seg_words + k],
  * f < nseg, k < seg_words = the 32-bit register (vfgs_hw.c:74-79) after first_bit + 32 * k steps from seeds[f] << 1 (vfgs_hw.c:343).

@@ -1561,11 +1561,12 @@ enum class Surface {
 	planar,            // three planes in, three planes out
 	semiplanar,        // sU == sV and dU == dV: the UV plane of interleaved Cb/Cr pairs, cstride its row in containers (KernelArgs::sp_kernel 1)
 	to_semiplanar,     // a planar source, dU == dV the UV plane (vfgs_hip_add_grain_frame_list_to_sp_dev / _to_sp8_dev; KernelArgs::sp_kernel 2)
+	to_planar,         // sU == sV the UV plane, three planes out (vfgs_hip_add_grain_sp_frame_list_to_planar_dev; KernelArgs::sp_kernel 3)
 };
 
-struct DstGeom {          // destination geometry when it differs from the source's: the 8-bit output of a 10- or 12-bit path, the surface of Surface::to_semiplanar
+struct DstGeom {          // destination geometry when it differs from the source's: the 8-bit output of a 10- or 12-bit path, the surface of Surface::to_semiplanar, the planes of Surface::to_planar
 	bool out8 = false;
-	unsigned stride = 0, cstride = 0;     // (to_semiplanar: the destination's rows in ITS containers -- out8: bytes)
+	unsigned stride = 0, cstride = 0;     // (to_semiplanar: the destination's rows in ITS containers -- out8: bytes; to_planar: in samples, cstride ONE component's row)
 	uint64_t ypitch = 0, cpitch = 0;
 };
 
@@ -1604,7 +1605,8 @@ struct GrainCall {
 // One run_device: the call, and what its phases hand to each other.
 struct Launch : GrainCall {
 	State& s;
-	const bool sp, p2sp;                    // (p2sp: planar source, semi-planar destination -- `sp`, both semi-planar, is false then)
+	const bool sp, p2sp;                    // (p2sp: planar source, semi-planar destination -- `sp`, a semi-planar source and its kernels, is false then)
+	const bool sp2p;                        // ... `sp` whose destination is three planes with a geometry of their own (dg)
 	KernelArgs a{};
 	bool nothing = false;                   // admitted, and nothing to launch (no lines, no frames)
 	unsigned nblk = 0, sz = 1, nparts = 1;  // nparts: passes over the parameter table a row needs
@@ -1618,7 +1620,7 @@ struct Launch : GrainCall {
 	long per_frame = 0, grid = 0;
 	vfgs::KernelKey key{};                   // which kernel serves the call (launch)
 
-	Launch(State& state, const GrainCall& c) : GrainCall(c), s(state), sp(surface == Surface::semiplanar), p2sp(surface == Surface::to_semiplanar) {}
+	Launch(State& state, const GrainCall& c) : GrainCall(c), s(state), sp(surface == Surface::semiplanar || surface == Surface::to_planar), p2sp(surface == Surface::to_semiplanar), sp2p(surface == Surface::to_planar) {}
 	int admit();
 	void plan_planes();
 	int plan_seeds();
@@ -1646,7 +1648,8 @@ int Launch::admit()
 	}
 	else if (!dg.out8)
 	{
-		if (int e = check_geometry(s, dY, dU, dV, width, stride, cstride, !mr)) return e;
+		// (a surface in, planes out: the destination's rows are the planar calls' -- Y, and ONE component's row of half as many samples)
+		if (int e = check_geometry(s, dY, dU, dV, width, sp2p ? dg.stride : stride, sp2p ? dg.cstride : cstride, !mr)) return e;
 	}
 	else
 	{
@@ -1658,7 +1661,7 @@ int Launch::admit()
 			return fail(8, "destination planes, pitches and frame pitches must be multiples of 16 bytes");
 	}
 	if (seeds && (frame_y != 0 || !list)) return fail(19, "internal: seeds belong to lists of frames that begin at line 0");
-	if (sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
+	if (sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || sU != sV || (sp2p ? dU == dV || dg.out8 : dU != dV) || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: semi-planar frames are listed whole frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
 	if (p2sp && (!list || frame_y != 0 || part_y != 0 || part_h != frame_h || dU != dV || s.csubx != 2 || width > (unsigned)vfgs::kTileBlocks * 16))
 		return fail(19, "internal: a planar source goes to listed whole semi-planar frames at 4:2:0 / 4:2:2 of at most %d samples a row", vfgs::kTileBlocks * 16);
@@ -1678,7 +1681,7 @@ int Launch::admit()
 	yext = (uint64_t)part_h * stride * sz; cext = crows * cstride * sz;
 	if (yext >= 0x80000000ull || cext >= 0x80000000ull)
 		return fail(15, "a plane stripe of %llu bytes exceeds the 2 GiB buffer window", (unsigned long long)yext);
-	if (p2sp)
+	if (p2sp || sp2p)
 	{
 		const uint64_t dsz = dg.out8 ? 1 : sz, dyext = (uint64_t)part_h * dg.stride * dsz, dcext = crows * dg.cstride * dsz;
 		if (dyext >= 0x80000000ull || dcext >= 0x80000000ull)
@@ -1706,6 +1709,7 @@ int Launch::admit()
 	// (a model per frame: the run's models carry a mix of their own -- depth and form were checked where it was attached -- and the programmed
 	// one, refused above, is not looked at)
 	mix = mr ? mr->mix : mix_active();
+	if (mix && sp2p) return fail(19, "internal: a semi-planar source with a planar destination under a chroma mix");     // (refused with code 40 at the entry; models that carry one: 41)
 	if (mix && p2sp) return fail(19, "internal: a planar source with a semi-planar destination under a chroma mix");     // (refused with code 40 at the entry; models that carry one: 41)
 	const int mix_code = sp ? 40 : 38;
 	const char* const mix_who = sp ? "semi-planar frames: " : "";
@@ -1735,12 +1739,12 @@ void Launch::plan_planes()
 			const unsigned subx = pt ? s.csubx : 1, suby = pt ? s.csuby : 1;
 			const unsigned bw = 16 / subx, rpb = 16 / suby;
 			d.pitch = (pt ? cstride : stride) * sz;
-			d.dpitch = dg.out8 ? (pt ? dg.cstride : dg.stride) : (p2sp ? (pt ? dg.cstride : dg.stride) * sz : d.pitch);
+			d.dpitch = dg.out8 ? (pt ? dg.cstride : dg.stride) : ((p2sp || sp2p) ? (pt ? dg.cstride : dg.stride) * sz : d.pitch);
 			d.fpitch = pt ? cpitch : ypitch;
 			d.dfpitch = dg.out8 ? (pt ? dg.cpitch : dg.ypitch) : d.fpitch;
 			// (semi-planar frames: "chroma" is the one plane of interleaved Cb/Cr pairs, a row of whole blocks as many containers as a luma row)
 			d.rowbytes = nblk * bw * sz * ((sp && pt) ? 2 : 1);
-			d.drowbytes = dg.out8 ? nblk * bw * ((sp && pt) ? 2 : 1) : d.rowbytes;      // (p2sp, chroma: ONE component's bytes of the UV row, vfgs_layout.h sp_kernel)
+			d.drowbytes = dg.out8 ? nblk * bw * ((sp && pt) ? 2 : 1) : ((sp2p && pt) ? d.rowbytes / 2 : d.rowbytes);      // (p2sp, chroma: ONE component's bytes of the UV row; sp2p, chroma: ONE component's row -- vfgs_layout.h sp_kernel)
 			d.nrows = pt ? (int)((part_y + part_h + suby - 1) / suby) - (int)((part_y + suby - 1) / suby) : (int)part_h;
 			auto lg = [](int v) { int l = 0; while ((1 << l) < v) l++; return l; };
 			const int ub = (sp && pt) ? vfgs::kSpUnitBytes : 16;   // (a lane's unit of an interleaved row: 32 bytes, vfgs_kernel.hip "UV walk")
@@ -1943,7 +1947,7 @@ int Launch::launch()
 	const bool p2sp_models = mr && !mix && (key.family == Family::p2sp || key.family == Family::p2sp8);
 	if (mr && !mix_models && !out8_models && !p2sp_models && key.family != Family::ml && key.family != Family::spml) return fail(19, "internal: a model per frame was admitted for a call that has no kernel with models");
 	if (mix_models && (key.out8 || key.wide)) return fail(19, "internal: models that carry a mix were admitted for a narrowed destination or rows walked in parts");
-	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models || out8_models || p2sp_models);
+	const vfgs::FamilyFields ff = vfgs::family_fields(key.family, mix_models || out8_models || p2sp_models, sp2p);     // (sp2p: the kernels of sp / spml, which decide at run time where the results go)
 	a.models_kernel = ff.models_kernel; a.mix_kernel = ff.mix_kernel; a.sp_kernel = ff.sp_kernel;
 	if (sp || p2sp) a.sp_shift2 = sample_shift * 0x10001u;
 	if (mix)
@@ -3399,10 +3403,11 @@ static int check_list(const ListCall& l)
 	const vfgs_hip_frame_ptrs *src = l.src, *dst = l.dst;
 	const unsigned nframes = l.nframes, width = g.width, stride = g.stride, cstride = g.cstride, part_y = g.part_y, part_h = g.part_h;
 	const DstGeom& dg = g.dg;
-	const bool sp = g.surface == Surface::semiplanar, p2sp = g.surface == Surface::to_semiplanar;     // (p2sp: dst[f].U == dst[f].V is the UV plane)
-	const bool dgeo = dg.out8 || p2sp;
+	const bool sp2p = g.surface == Surface::to_planar;     // (src[f].U == src[f].V is the UV plane, the destination three planes)
+	const bool sp = g.surface == Surface::semiplanar || sp2p, p2sp = g.surface == Surface::to_semiplanar;     // (p2sp: dst[f].U == dst[f].V is the UV plane)
+	const bool dgeo = dg.out8 || p2sp || sp2p;
 	const int ncomp = sp ? 2 : 3;     // planes of a source frame ...
-	const int ncomp_d = (sp || p2sp) ? 2 : 3;     // ... and of a destination frame
+	const int ncomp_d = ((sp && !sp2p) || p2sp) ? 2 : 3;     // ... and of a destination frame
 	const State& s = S();
 	if (!src || !dst) return fail(18, "frame list: null list");
 	for (unsigned f = 0; f < nframes; f++)
@@ -3418,14 +3423,14 @@ static int check_list(const ListCall& l)
 	// ANOTHER (that frame may already have been grained when it is read).  The bytes of a plane: its rows of the stripe, whole
 	// 16-sample blocks each (check_geometry).  A frame's own source and destination are either the same plane (in place) or disjoint.
 	// (semi-planar frames with the narrowed destination: containers of another size, so there is no in-place form -- disjoint, always)
-	const bool no_in_place = (sp && dg.out8) || p2sp;
+	const bool no_in_place = (sp && dg.out8) || p2sp || sp2p;
 	{
 		const uint64_t sz = s.bs ? 2 : 1, nblk = (width + 15) / 16;
 		const uint64_t crows = part_h ? (uint64_t)(part_y + part_h - 1) / s.csuby - part_y / s.csuby + 1 : 0;
 		const uint64_t dsz = dg.out8 ? 1 : sz, dstr = dgeo ? dg.stride : stride, dcstr = dgeo ? dg.cstride : cstride;
 		auto extent = [&](uint64_t rows, uint64_t pitch, uint64_t rowb) { return rows ? (rows - 1) * pitch + rowb : 0; };
 		const uint64_t cblk = sp ? 16 : 16 / s.csubx;     // containers of a grain block in a chroma row (semi-planar: Cb and Cr)
-		const uint64_t cblk_d = p2sp ? 16 : cblk;         // ... of the destination
+		const uint64_t cblk_d = p2sp ? 16 : (sp2p ? 8 : cblk);         // ... of the destination
 		const uint64_t ext_s[3] = {extent(part_h, stride * sz, nblk * 16 * sz), extent(crows, cstride * sz, nblk * cblk * sz), 0};
 		const uint64_t ext_d[3] = {extent(part_h, dstr * dsz, nblk * 16 * dsz), extent(crows, dcstr * dsz, nblk * cblk_d * dsz), 0};
 		struct Span { uintptr_t lo, hi; unsigned frame; };
@@ -4033,6 +4038,57 @@ int vfgs_hip_add_grain_frame_list_models_to_sp8_dev(const vfgs_hip_frame_ptrs* s
 	std::lock_guard<std::mutex> g(g_mu);
 	return run_to_sp(src, dst, seeds, nframes, GrainCall().rows(width, stride, cstride).whole(height).to(Surface::to_semiplanar, 0).dst_rows(true, dst_stride, dst_uv_stride), stream,
 	                 true, models);
+}
+
+// A semi-planar source, a planar destination (vfgs_hip.h): what a hardware decoder hands out goes to the planes a software encoder, the planar
+// calls or a tensor per plane take.  The semi-planar list call with a destination geometry of its own and three destination planes; no kernel of
+// its own: grain_sp_kernel / grain_spml_kernel decide at run time where the results go (KernelArgs::sp_kernel 3).  The checks of run_to_sp with
+// source and destination swapped, in its order.
+static int run_sp_to_planar(const vfgs_hip_sp_frame* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds, unsigned nframes, const GrainCall& c, void* stream,
+                            const bool with_models = false, const vfgs_hip_model* const* models = nullptr)
+{
+	State& s = S();
+	s.gen++;
+	if (int e = ensure_init(-1)) return e;
+	if (nframes == 0) return 0;
+	const char* const who = with_models ? "semi-planar to planar with models" : "semi-planar to planar";
+	if (int e = check_semiplanar(who, s, c.sample_shift, c.width)) return e;
+	if (!with_models && mix_active())
+		return fail(40, "semi-planar to planar: a chroma mix is active; the mix stays with the calls that honour it (grain the surface with the semi-planar call)");
+	if (!src || !dst) return fail(18, "frame list: null list");
+	// (the destination's pitches, with the codes of the planar calls: ONE component's row is half as many samples as the luma row)
+	const unsigned nb16 = (c.width + 15) / 16 * 16, dsz = s.bs ? 2 : 1;
+	if (c.dg.stride < nb16 || c.dg.cstride < nb16 / 2)
+		return fail(6, "destination stride %u/%u too small: whole 16-sample blocks are written (need >= %u/%u)", c.dg.stride, c.dg.cstride, nb16, nb16 / 2);
+	if ((c.dg.stride * dsz) % 16 || (c.dg.cstride * dsz) % 16) return fail(8, "destination row pitches must be multiples of 16 bytes");
+	const std::vector<vfgs_hip_frame_ptrs> ps = three_planes(src, nframes);
+	ListCall l(ps.data(), dst, nframes, seeds, stream, c);
+	if (with_models) l.with(models);     // (before the list checks: the scale shift that counts is each model's)
+	if (int e = check_list(l)) return e;
+	if (with_models)
+	{
+		if (int e = check_models_window(l)) return e;
+		if (int e = check_models(who, s, models, nframes, 0)) return e;     // (width: refused above, under 40)
+		if (int e = check_models_without_mix(who, models, nframes, "the mix stays with the calls that honour it")) return e;
+	}
+	return launch_list(l);
+}
+
+int vfgs_hip_add_grain_sp_frame_list_to_planar_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_frame_ptrs* dst, const uint32_t* seeds, unsigned nframes,
+                                                   unsigned width, unsigned height, unsigned stride, unsigned uv_stride, unsigned dst_stride,
+                                                   unsigned dst_cstride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return run_sp_to_planar(src, dst, seeds, nframes, GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::to_planar, sample_shift).dst_rows(false, dst_stride, dst_cstride), stream);
+}
+
+int vfgs_hip_add_grain_sp_frame_list_models_to_planar_dev(const vfgs_hip_sp_frame* src, const vfgs_hip_frame_ptrs* dst, const vfgs_hip_model* const* models,
+                                                          const uint32_t* seeds, unsigned nframes, unsigned width, unsigned height, unsigned stride,
+                                                          unsigned uv_stride, unsigned dst_stride, unsigned dst_cstride, unsigned sample_shift, void* stream)
+{
+	std::lock_guard<std::mutex> g(g_mu);
+	return run_sp_to_planar(src, dst, seeds, nframes, GrainCall().rows(width, stride, uv_stride).whole(height).to(Surface::to_planar, sample_shift).dst_rows(false, dst_stride, dst_cstride), stream,
+	                        true, models);
 }
 
 int vfgs_hip_add_grain_frames_host(void* const* Y, void* const* U, void* const* V, unsigned nframes, unsigned width,

@@ -685,6 +685,12 @@ constexpr int ring_depth() { return (DEPTH == 8 && ONE && kPk16) ? VFGS_RING_PK 
 //     SP = 2 (luma planes of grain_p2sp_kernel / grain_p2sp8_kernel: a PLANAR source, a semi-planar destination): the source is read as it lies,
 //     low-aligned -- nothing is shifted down -- the results go up or are narrowed as above, and the destination has a geometry of its own
 //     (dpitch, drowbytes) at either container size.
+//     SP = 3 (luma planes of grain_sp_kernel / grain_spml_kernel): SP = 1 whose destination may be a PLANAR picture, decided at RUN time by
+//     KernelArgs::sp_kernel == 3 (vfgs_hip_add_grain_sp_frame_list_to_planar_dev) without a branch: the walk always stores through the
+//     destination's own geometry -- for a surface the host passes the source's (dpitch == pitch, drowbytes == rowbytes) -- and the shift up
+//     comes from a scalar that is 0 where the destination holds low-aligned samples.  (A second instantiation chosen per workgroup, as the UV
+//     walk has it, was built and costs MORE registers: the scalars it spills take vector registers of the whole kernel, and the 8-bit
+//     general-form kernels then spill two of those to scratch.)
 //   * MODELS (grain_ml_kernel, and with SP the luma planes of grain_spml_kernel: a model per frame): the table image, the clip bounds and the packed form's shift are those of the
 //     workgroup's FRAME -- FrameTable::model[f] points at a ModelRecord with the image behind it -- fetched with scalar loads (the pointer from
 //     the kernel arguments, the record through it) in front of the image loads; everything they feed stays wave-uniform.  Without the flag
@@ -726,7 +732,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	static_assert(!MIX || (ONE && NARROW == 0 && !PERSIST), "the mix exists for one-pattern chroma walked row by row");
 	static_assert(!SP || (NARROW == 0 && !WIDE && !PERSIST && !MIX), "semi-planar frames: the plain luma walk (OUT8: of grain_sp8_kernel)");
 	static_assert(!MODELS || (!WIDE && !PERSIST && (!MIX || MODELS == 2) && (SP != 2 || (MODELS == 2 && !MIX)) && (!OUT8 || (MODELS == 2 && !MIX))), "a model per frame: the plain walk (SP: the luma of grain_spml_kernel), one task per workgroup; under the mix, with the narrowed destination and from a planar source onto a surface: decided at run time");
-	constexpr bool DGEO = OUT8 || SP == 2;               // the destination has a geometry of its own
+	constexpr bool DGEO = OUT8 || SP == 2 || SP == 3;    // the destination has a geometry of its own
 	const int pt = comp ? 1 : 0;
 	auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
@@ -954,6 +960,8 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 	};
 
 	// ---- the walk ----------------------------------------------------------------------------------------------------
+	// SP = 3: what the results go up by -- nothing where the destination is a planar picture (KernelArgs::sp_kernel == 3)
+	const uint32_t up2 = (SP == 3 && a.sp_kernel != 3) ? a.sp_shift2 : 0u;
 	uint32_t carry[4] = {0, 0, 0, 0};      // in lane 0: the last K dwords of lane 63 of the previous position of the row
 	uint32_t mcarry[4] = {0, 0, 0, 0};     // MIX: the same for the index dwords
 	const int mixc = comp == 2 ? 1 : 0;
@@ -1084,7 +1092,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				// assemble my 16 bytes: the last K dwords of the unit of the lane before me, the first 4 - K of mine
 				uint32_t t[4];
 				uint32_t ti[4] = {};
-				if constexpr (SP == 1 && DEPTH > 8)
+				if constexpr ((SP == 1 || SP == 3) && DEPTH > 8)
 				{
 #pragma unroll
 					for (int d = 0; d < 4; d++) w[u][d] = pk_lshr_b16(a.sp_shift2, w[u][d]);
@@ -1151,7 +1159,7 @@ __device__ __forceinline__ void run_plane_rw(const KernelArgs& a, const FrameTab
 				if constexpr (SP && DEPTH > 8 && !OUT8)     // (the narrowed destination holds plain bytes)
 				{
 #pragma unroll
-					for (int d = 0; d < DW; d++) o[d] = pk_lshl_b16(a.sp_shift2, o[d]);
+					for (int d = 0; d < DW; d++) o[d] = pk_lshl_b16(SP == 3 ? up2 : a.sp_shift2, o[d]);
 				}
 				// the previous position's units are complete once the KD dwords its lanes computed have moved one lane down; its
 				// lane 63 takes them from my lane 0 (the previous position of a row's first one is the last of another row:
@@ -1399,7 +1407,16 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kMixWgPerCU) void grain_mix_kerne
 // Cb/Cr byte pairs are clipped with the frame's chroma bounds (lo2 / hi2 below are one pair for the two grain_unit calls of a position).
 // MODELS = 2 with PLANAR (UV workgroups of grain_p2sp_kernel / grain_p2sp8_kernel): the same run-time decision; both components of a Cb/Cr pair
 // take the frame's chroma bounds.
-template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, int MODELS = 0>
+//
+// TOPL, A PLANAR DESTINATION (UV workgroups of grain_sp_kernel / grain_spml_kernel -- neither MIX, OUT8 nor PLANAR -- where KernelArgs::sp_kernel == 3:
+// vfgs_hip_add_grain_sp_frame_list_to_planar_dev): decided at RUN time by the kernel, ONCE per workgroup -- a wave-uniform branch between two
+// instantiations of this function, so that the walk onto a surface keeps the instructions and the registers it had before there was a choice (one
+// walk with the branch at the store spilled vector registers in the 8-bit general-form kernels, which sit at 126 of 128).  The walk is the one above
+// up to the two planar result units; they are neither joined nor shifted up, and go as 16 bytes each to the Cb row and to the Cr row, through a
+// descriptor per component (FrameTable::dst[1] / [2]; pd.dpitch and pd.drowbytes describe ONE component's destination row, the range check is per
+// component row: an 8-bit row of an odd number of blocks ends in half a 16-byte unit and the 8 bytes behind it are never written).  The kernels with
+// MIX, OUT8 or PLANAR hold nothing of this.
+template <int DEPTH, int SUBY, int RS, int CIMG, int BANK, bool ONE, int NEG, bool MIX = false, bool OUT8 = false, bool PLANAR = false, int MODELS = 0, bool TOPL = false>
 __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable& ft, uint8_t* lds, const int f, const int r, const uint32_t img_off, const int lane, const int wave)
 {
 	constexpr int NS = DEPTH == 8 ? 16 : 8;
@@ -1420,6 +1437,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	static_assert(!PLANAR || !MIX, "a planar source has no mix form");
 	static_assert(!MODELS || ((OUT8 || PLANAR) ? (MODELS == 2 && !MIX) : MIX == (MODELS == 2)), "a model per frame: the plain UV walk; under the mix, with the narrowed destination and from a planar source: decided at run time");
 	constexpr bool DGEO = OUT8 || PLANAR;                // the destination has a geometry of its own
+	static_assert(!TOPL || (!OUT8 && !PLANAR && !MIX), "planes out: the kernels of the plain UV walk alone");
 	constexpr int LDA = VFGS_LDAUX_ALIGNED, STA = VFGS_STAUX_ALIGNED;
 	constexpr int LUTB = 2 * 256 * 4;                    // a component's pair of tables (general form)
 	constexpr int IMG = sp_uv_image_bytes(CIMG, LUTB, ONE);
@@ -1503,6 +1521,8 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	const uint8_t* sbase = a.listed ? ft.src[1][f] : a.src[1] + (uint64_t)f * pd.fpitch;
 	const uint8_t* sbase2 = PLANAR ? (a.listed ? ft.src[2][f] : a.src[2] + (uint64_t)f * pd.fpitch) : nullptr;     // PLANAR: the Cr plane (sbase: the Cb plane)
 	uint8_t* dbase = a.listed ? ft.dst[1][f] : a.dst[1] + (uint64_t)f * pd.dfpitch;
+	// TOPL: the destination is planar; dbase is its Cb plane and dbase2 its Cr plane (semi-planar frames are listed, always: launch_args_ok)
+	uint8_t* dbase2 = TOPL ? ft.dst[2][f] : nullptr;
 	const uint32_t lane32 = (uint32_t)lane * kSpUnitBytes;
 	constexpr uint32_t UBI = kMaxUnits * kSpUnitBytes;   // bytes of a position of an interleaved row
 	constexpr uint32_t UB = PLANAR ? kMaxUnits * 16 : UBI;     // bytes of a position of the source (PLANAR: of each component's row)
@@ -1514,6 +1534,9 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	constexpr uint32_t UBD = OUT8 ? kMaxUnits * 16 : UBI, GBD = NU * UBD;
 	auto row_offd = [&](int k) { return (uint32_t)((base + RSTR * k - prow0) * (int)pd.dpitch); };
 	auto leftd = [&](int g) { const uint32_t o = (uint32_t)g * GBD, rb = PLANAR ? 2 * pd.drowbytes : pd.drowbytes; return o < rb ? min(rb - o, GBD) : 0u; };
+	// (TOPL: a position of ONE component's destination row is 1 KiB, a lane's unit 16 bytes)
+	constexpr uint32_t UBP = kMaxUnits * 16, GBP = NU * UBP;
+	auto leftp = [&](int g) { const uint32_t o = (uint32_t)g * GBP; return o < pd.drowbytes ? min(pd.drowbytes - o, GBP) : 0u; };
 	uint32_t w[NU][8];
 	// (rs2: PLANAR only -- the Cr row; w[u][0..3] is the Cb unit and w[u][4..7] the Cr unit)
 	auto load_pos = [&](const __amdgpu_buffer_rsrc_t rs, const __amdgpu_buffer_rsrc_t rs2, const int u) {
@@ -1613,7 +1636,35 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	const int mix_off[2] = {MIX ? own(pick(0, 2)) : 0, MIX ? own(pick(1, 2)) : 0};
 	const bool mix_on[2] = {MIX && own(pick(0, 3)) != 0, MIX && own(pick(1, 3)) != 0};
 	__amdgpu_buffer_rsrc_t pdst = make_rsrc(dbase, 0);
+	// TOPL: where the previous group's last position goes is kept as the Cb row's address and what ONE component's row has left there; the two
+	// descriptors are made at the store, the Cr row's from the distance between the two planes.  (Four descriptors kept across the walk are
+	// sixteen scalar registers; spilled scalars take a vector register of the whole kernel, and the 8-bit general-form kernels have none to give.)
+	uint8_t* pptr = dbase;
+	uint32_t plen = 0;
+	const ptrdiff_t cr_from_cb = TOPL ? dbase2 - dbase : 0;
 	// the previous position is complete: interleave its two planar units, shift them up, store 32 bytes
+	// (store_planar, TOPL only: a planar destination takes the two units as they are, low-aligned, 16 bytes to the Cb row and 16 to the Cr row;
+	// `off` counts bytes of the interleaved row, a component's row has half of them)
+	auto store_planar = [&](uint8_t* const cb, const uint32_t len, const uint32_t off) {
+		if constexpr (TOPL)
+		{
+			// The two asm statements below STEER the register allocator, they force nothing, and they are fitted to one compiler's allocator: their
+			// only guard is tests/test_code_object_sp_to_planar_cpu.py (no scratch, no spilled vector register in the 48 kernels).  If a new ROCm
+			// makes that test fail, this is the place to revisit -- and if the plain form (voff = lane * 16, outp[] as the stores' data) then fits,
+			// take it.
+			// (the lane's offset in a component's row is half its offset in the interleaved row: made here, not kept beside lane32)
+			uint32_t voff;
+			asm volatile("v_lshrrev_b32 %0, 1, %1" : "=v"(voff) : "v"(lane32));
+			// (real copies, as the interleave makes them: were outp[] itself the store's data, each unit would have to sit in four consecutive
+			// registers from one position to the next, apart from the results it is refilled from -- eight registers the 8-bit general-form
+			// kernels do not have)
+			uint32_t st[2][4];
+#pragma unroll
+			for (int q = 0; q < 8; q++) asm volatile("v_mov_b32 %0, %1" : "=v"(st[q / 4][q % 4]) : "v"(outp[q / 4][q % 4]));
+			store_unit<4, STA>(make_rsrc(cb, len), voff + off / 2, st[0]);
+			store_unit<4, STA>(make_rsrc(cb + cr_from_cb, len), voff + off / 2, st[1]);
+		}
+	};
 	auto store_prev = [&](const __amdgpu_buffer_rsrc_t rs, const uint32_t off) {
 		if constexpr (OUT8)
 		{
@@ -1656,6 +1707,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	};
 	auto walk_row = [&](auto overlap, const int k) {
 		constexpr bool OV = decltype(overlap)::value;
+		constexpr bool TP = TOPL;
 		const int j = base + RSTR * k - Rabs * RPB;    // row inside the block row
 		const int jrow = j * SUBY;
 		const uint32_t rowoff = (uint32_t)j * RS, uprowoff = (uint32_t)(RPB + j) * RS;
@@ -1680,7 +1732,11 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 			const __amdgpu_buffer_rsrc_t nsrc = make_rsrc(sbase + nso, nvalid ? left(ng) : 0u);
 			const __amdgpu_buffer_rsrc_t nsrc2 = PLANAR ? make_rsrc(sbase2 + nso, nvalid ? left(ng) : 0u) : nsrc;
 			const __amdgpu_buffer_rsrc_t nlsrc = make_rsrc(lbase + (MIX && nvalid ? (lastg ? lrow_off(k + 1) : lro) + (uint32_t)ng * GB : 0u), MIX && nvalid ? left(ng) : 0u);
-			const __amdgpu_buffer_rsrc_t cdst = DGEO ? make_rsrc(dbase + (row_offd(k) + (uint32_t)g * GBD), leftd(g)) : make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g));
+			// (TP: this group of the Cb row, and what ONE component's row has left from there; no descriptor is kept)
+			uint8_t* const cptr = TP ? dbase + (row_offd(k) + (uint32_t)g * GBP) : nullptr;
+			const uint32_t clen = TP ? leftp(g) : 0u;
+			const __amdgpu_buffer_rsrc_t cdst = TP ? pdst
+			                                  : (DGEO ? make_rsrc(dbase + (row_offd(k) + (uint32_t)g * GBD), leftd(g)) : make_rsrc(dbase + (ro + (uint32_t)g * GB), left(g)));
 			const uint8_t* pe = lds + idx0 + (uint32_t)(g * NU * BPS * 4);
 			const int clg = cl + g * NU * BPS;
 #pragma unroll
@@ -1788,8 +1844,16 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 						for (int d = 0; d < K; d++) outp[c][4 - K + d] = lane_down(rot_down(t[d]), tp[c][d]);
 					}
 				}
-				if (u == 0) store_prev(pdst, (NU - 1) * UBD);
-				else store_prev(cdst, (u - 1) * UBD);
+				if constexpr (TP)
+				{
+					if (u == 0) store_planar(pptr, plen, (NU - 1) * UBD);
+					else store_planar(cptr, clen, (u - 1) * UBD);
+				}
+				else
+				{
+					if (u == 0) store_prev(pdst, (NU - 1) * UBD);
+					else store_prev(cdst, (u - 1) * UBD);
+				}
 #pragma unroll
 				for (int c = 0; c < 2; c++)
 				{
@@ -1813,6 +1877,7 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 #endif
 			}
 			pdst = cdst;
+			if constexpr (TP) { pptr = cptr; plen = clen; }
 		}
 	};
 	for (int k = k0; k < k1; k++)
@@ -1826,11 +1891,15 @@ __device__ __forceinline__ void run_uv_sp(const KernelArgs& a, const FrameTable&
 	for (int c = 0; c < 2; c++)
 #pragma unroll
 		for (int d = 0; d < KD; d++) outp[c][DW - KD + d] = lane_down(0u, tp[c][d]);
-	store_prev(pdst, (NU - 1) * UBD);
+	if constexpr (TOPL) store_planar(pptr, plen, (NU - 1) * UBD);
+	else store_prev(pdst, (NU - 1) * UBD);
 }
 
 // The kernels of semi-planar frames (KernelArgs::sp_kernel): the grid and the workgroup numbering of grain_rw_kernel with ONE UV workgroup where
 // that has a Cb and a Cr workgroup.  kSpWgPerCU (vfgs_layout.h) workgroups per CU in every form: a UV wave keeps two components' walks alive.
+// KernelArgs::sp_kernel == 3 (vfgs_hip_add_grain_sp_frame_list_to_planar_dev): the same kernels store planar pictures, decided at run time: the luma
+// walk without a branch (run_plane_rw SP = 3), the UV walk once per workgroup between two instantiations (run_uv_sp TOPL); grain_spml_kernel below
+// likewise.  Guard of the registers this was fitted into: tests/test_code_object_sp_to_planar_cpu.py.
 template <int DEPTH, int CSUBY, bool ONEY, bool ONEC>
 __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp_kernel(const KernelArgs a, const FrameTable ft)
 {
@@ -1843,7 +1912,9 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_sp_kernel(
 	const int r = (int)(blockIdx.x >> a.lfronts);
 	if (f >= a.nframes) return;
 	if (r < a.pd[0].wgs)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, 3>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else if (a.sp_kernel == 3)      // planes out (run_uv_sp TOPL): one branch per workgroup
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, false, 0, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 	else
 		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 }
@@ -1863,7 +1934,9 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kSpWgPerCU) void grain_spml_kerne
 	const int r = (int)(blockIdx.x >> a.lfronts);
 	if (f >= a.nframes) return;
 	if (r < a.pd[0].wgs)
-		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, true, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+		run_plane_rw<DEPTH, 16, 1, 1, L.y_rs, L.y_bytes, ONEY, L.y_neg, 0, false, false, false, false, 3, true>(a, ft, a.pd[0], lds, 0, f, r, L.y_off, L.y_bank, 0, lane, wave);
+	else if (a.sp_kernel == 3)      // planes out (run_uv_sp TOPL): one branch per workgroup
+		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, false, true, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 	else
 		run_uv_sp<DEPTH, CSUBY, L.c_rs, L.c_bytes, L.c_bank, ONEC, L.c_neg, false, false, false, true>(a, ft, lds, f, r - a.pd[0].wgs, L.c_off[0], lane, wave);
 }
@@ -1996,7 +2069,10 @@ static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const Ke
 	if (out8_models && !(k.out8 && !k.wide && !k.persist)) return false;
 	// (and every kernel of a planar source with a semi-planar destination: listed frames with a 16-byte-aligned model image each, held to that below)
 	const bool p2sp_models = (f == Family::p2sp || f == Family::p2sp8) && a.models_kernel != 0;
-	const FamilyFields ff = family_fields(f, mix_models || out8_models || p2sp_models);
+	// (a surface in, planes out: the kernels of sp / spml alone decide that at run time)
+	const bool to_planar = a.sp_kernel == 3;
+	if (to_planar && f != Family::sp && f != Family::spml) return false;
+	const FamilyFields ff = family_fields(f, mix_models || out8_models || p2sp_models, to_planar);
 	if (a.models_kernel != ff.models_kernel || a.mix_kernel != ff.mix_kernel || a.sp_kernel != ff.sp_kernel) return false;
 	if (k.wide != (a.nblk > kTileBlocks)) return false;
 	if (a.mix_kernel ? (a.mix_lw < 1 || a.mix_lw > a.nblk * kBlock) : a.mix_planes != 0) return false;
@@ -2026,6 +2102,17 @@ static bool launch_args_ok(const KernelArgs& a, const FrameTable* list, const Ke
 		if (planar_src && a.pd[0].rowbytes != 2 * a.pd[1].rowbytes) return false;
 	}
 	if (f == Family::sp_mix && a.pd[0].rowbytes != a.pd[1].rowbytes) return false;
+	if (to_planar)
+	{
+		// a planar destination's own geometry: a luma row of the source's bytes, ONE component's half of a UV row's, pitches that hold them in
+		// whole 16-byte units, three planes a frame
+		if (a.pd[0].drowbytes != a.pd[0].rowbytes || 2 * a.pd[1].drowbytes != a.pd[1].rowbytes) return false;
+		if (a.pd[0].dpitch < a.pd[0].drowbytes || a.pd[1].dpitch < a.pd[1].drowbytes || ((a.pd[0].dpitch | a.pd[1].dpitch) & 15)) return false;
+		for (int i = 0; i < a.nframes; i++)
+			if (!list->dst[0][i] || !list->dst[1][i] || !list->dst[2][i] || list->dst[1][i] == list->dst[2][i]) return false;
+	}
+	// (the luma walk of the two families always stores through the destination's geometry: for a surface it is the source's)
+	else if ((f == Family::sp || f == Family::spml) && (a.pd[0].dpitch != a.pd[0].pitch || a.pd[0].drowbytes != a.pd[0].rowbytes)) return false;
 	return true;
 }
 

@@ -344,6 +344,9 @@ struct KernelArgs {
 	                          // 2: grain_p2sp_kernel (out8: grain_p2sp8_kernel): the SOURCE is planar -- src[1] / src[2] are two planes, pd[1].pitch / rowbytes ONE
 	                          //    component's row -- the destination is such a UV plane: dst[1] == dst[2], pd[1].dpitch its row pitch and pd[1].drowbytes ONE
 	                          //    component's bytes of its row (the row holds twice as many); pd[0].dpitch / drowbytes: the destination's luma row
+	                          // 3: grain_sp_kernel (with models_kernel: grain_spml_kernel) again, the source as for 1 -- the DESTINATION is planar: dst[1] / dst[2]
+	                          //    are the Cb and the Cr plane of low-aligned samples, pd[1].dpitch / drowbytes ONE component's destination row, pd[0].dpitch /
+	                          //    drowbytes the destination's luma row (vfgs_hip_add_grain_sp_frame_list_to_planar_dev); the kernels decide at run time
 	uint32_t sp_shift2;       // ... 16-bit containers: the samples sit this many bits up (P010: 6, P012: 4), in both halves of the dword (a packed 16-bit shift each way)
 	// The phase between the two frame fronts (front_phase / front_task below; both zero = the fronts in step, every kernel but grain_rw_kernel)
 	int front_shift;          // tasks by which the odd front of a pair of frames is rotated: it runs task (r + front_shift) mod per-frame tasks where the even front runs task r
@@ -412,13 +415,14 @@ constexpr bool family_semiplanar(const Family f) { return f != Family::rw && f !
 // the same kernels, which decide at run time where the image, the bounds and the mix come from -- or of rw / sp8 with the narrowed destination
 // (the key has out8, neither wide nor persist; the launcher holds it to that): the OUT8 kernels decide the same way -- or of p2sp / p2sp8 (a planar
 // source onto a surface with a model per frame: every kernel of the two families decides the same way).  Every other family has one answer.
+// to_planar: a launch of sp / spml whose destination is a planar picture (sp_kernel 3; the same kernels decide at run time).  No other family has such a form.
 struct FamilyFields { int models_kernel, mix_kernel, sp_kernel; };
-constexpr FamilyFields family_fields(const Family f, const bool with_models = false)
+constexpr FamilyFields family_fields(const Family f, const bool with_models = false, const bool to_planar = false)
 {
 	const bool mixf = f == Family::mix || f == Family::sp_mix;
 	const bool run_time = mixf || f == Family::rw || f == Family::sp8 || f == Family::p2sp || f == Family::p2sp8;     // the families whose kernels serve programmed launches and models alike
 	return FamilyFields{f == Family::ml || f == Family::spml || (run_time && with_models), mixf,
-	                    !family_semiplanar(f) ? 0 : ((f == Family::p2sp || f == Family::p2sp8) ? 2 : 1)};
+	                    !family_semiplanar(f) ? 0 : ((f == Family::p2sp || f == Family::p2sp8) ? 2 : ((to_planar && (f == Family::sp || f == Family::spml)) ? 3 : 1))};
 }
 
 // THE TABLE OF INSTANTIATIONS.  A family pins every parameter it does not take, so one kernel has exactly one key.

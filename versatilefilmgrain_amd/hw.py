@@ -139,6 +139,8 @@ def load(path: Path | None = None) -> C.CDLL:
     lib.vfgs_hip_add_grain_sp_frame_list_models_copy8_dev.argtypes = [spf, spf, C.POINTER(vp), sp, u, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_models_to_sp_dev.argtypes = [fp, spf, C.POINTER(vp), sp, u, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_add_grain_frame_list_models_to_sp8_dev.argtypes = [fp, spf, C.POINTER(vp), sp, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_sp_frame_list_to_planar_dev.argtypes = [spf, fp, sp, u, u, u, u, u, u, u, u, vp]
+    lib.vfgs_hip_add_grain_sp_frame_list_models_to_planar_dev.argtypes = [spf, fp, C.POINTER(vp), sp, u, u, u, u, u, u, u, u, vp]
     lib.vfgs_hip_seed_segments.argtypes = [sp, u, C.c_uint64, u, sp]
     lib.vfgs_hip_get_seeded_stream_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.vfgs_hip_get_seeded_stream_stats.restype = None
@@ -222,6 +224,7 @@ EXPORTS = [
     "vfgs_hip_add_grain_sp_frame_list_models_dev", "vfgs_hip_model_image", "vfgs_hip_get_model_build_stats",
     "vfgs_hip_add_grain_frame_list_models_copy8_dev", "vfgs_hip_add_grain_sp_frame_list_models_copy8_dev",
     "vfgs_hip_add_grain_frame_list_models_to_sp_dev", "vfgs_hip_add_grain_frame_list_models_to_sp8_dev",
+    "vfgs_hip_add_grain_sp_frame_list_to_planar_dev", "vfgs_hip_add_grain_sp_frame_list_models_to_planar_dev",
     "vfgs_hip_host_pipe_open", "vfgs_hip_host_pipe_submit", "vfgs_hip_host_pipe_wait", "vfgs_hip_host_pipe_close",
 ]
 
@@ -563,6 +566,30 @@ class VfgsHip:
         arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
         self._ck(self.lib.vfgs_hip_add_grain_frame_list_models_to_sp8_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride, cstride,
                                                                           dst_stride, dst_uv_stride, stream))
+
+    def add_grain_sp_frame_list_to_planar_dev(self, src, dst, seeds, width, height, stride, uv_stride, dst_stride, dst_cstride, sample_shift, stream=0):
+        """Semi-planar surfaces in, planar frames out (P010 -> yuv420p10le, NV12 -> yuv420p ...): src a list of (Y, UV) addresses as in
+        add_grain_sp_frame_list_dev (strides in containers, sample_shift 0 or 16 - depth: the SOURCE's), dst a list of (Y, U, V) addresses of
+        planar, low-aligned pictures (strides in samples), never in place; seeds None: one seed sequence, else a seed per picture.  Every
+        sample is the out-of-place semi-planar call's container >> sample_shift, Cb and Cr de-interleaved.  An active chroma mix:
+        VfgsHipError 40; a destination that shares bytes with another destination plane or any source plane: 18 (include/vfgs_hip.h)."""
+        s, d = self.sp_frame_list(src), self.frame_list(dst)
+        assert len(s) == len(d) and (seeds is None or len(seeds) == len(s))
+        self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_to_planar_dev(s, d, self.seed_list(seeds), len(s), width, height, stride, uv_stride,
+                                                                         dst_stride, dst_cstride, sample_shift, stream))
+
+    def add_grain_sp_frame_list_models_to_planar_dev(self, src, dst, models, seeds, width, height, stride, uv_stride, dst_stride, dst_cstride,
+                                                     sample_shift, stream=0):
+        """... with a model per picture: src / dst / strides / sample_shift as in add_grain_sp_frame_list_to_planar_dev, models and seeds as in
+        add_grain_sp_frame_list_models_dev.  Frame f gets the samples of a one-frame add_grain_sp_frame_list_to_planar_dev with models[f]'s
+        state programmed (and, with seeds, vfgs_set_seed(seeds[f]) called); one launch per run of at most 32 frames whose models share the
+        form of their images; the programmed state is unchanged.  VfgsHipError 40: csubx != 2, a bad sample_shift, width > 8192; 41: a null /
+        released model, a model of another depth or chroma format, an active chroma mix, a model that carries a mix (include/vfgs_hip.h)."""
+        s, d = self.sp_frame_list(src), self.frame_list(dst)
+        assert len(s) == len(d) == len(models) and (seeds is None or len(seeds) == len(s))
+        arr = models if isinstance(models, C.Array) else (C.c_void_p * len(models))(*models)
+        self._ck(self.lib.vfgs_hip_add_grain_sp_frame_list_models_to_planar_dev(s, d, arr, self.seed_list(seeds), len(s), width, height, stride,
+                                                                                uv_stride, dst_stride, dst_cstride, sample_shift, stream))
 
     def seed_segments(self, seeds, first_bit, seg_words):
         """What a seeded launch uploads (host only): a list of len(seeds) lists of seg_words registers (include/vfgs_hip.h)."""
